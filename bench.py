@@ -8,6 +8,11 @@ device with the reference's gen_data mode 5 before the timed region).
 
   value       = sum of algorithmic flops of every op launched on every rank in
                 the timed steps / max-over-ranks wall time    [GFLOP/s]
+  ms_per_step = max-over-ranks wall time of the --steps timed steps / --steps
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line with
+the figures above. --full goes on to measure the rest (runs of their own after the timed region):
+
   per_set     = per op-list aggregate in the reference's own convention:
                 sum flops / sum per-op GPU seconds (src/rtc_prof.cc:104-124),
                 plus sum(roofline time) / sum(kernel time)
@@ -166,17 +171,53 @@ def cpu_baseline(budget_s):
     return line
 
 
+DUMP_CAP_BYTES = 48 << 20  # all of --dump-outputs together (every rank's share of it)
+DUMP_SAMPLE = 32768  # floats kept of a larger output (the 399 default units: at most 49.9 MiB)
+
+
+def dump_outputs(wl, mine, units, tags, out_dir, rank):
+    """Write what the timed steps left in the output buffer of each of this rank's units (c of an SGEMM,
+    out of a conv: what a caller of the step receives) as out_dir/<set>_op<index>.npy, float32; a column
+    panel of an SGEMM cut up for N > 1 ranks as <set>_op<index>_r<rank>p<k>.npy, k counting the op's panels
+    on that rank. An output of more floats than the sample size is written as a fixed sample: the flat
+    positions drawn by a generator seeded with the op's index, in drawing order, so the same arguments
+    give the same positions in every run and build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sample = min(DUMP_SAMPLE, DUMP_CAP_BYTES // (4 * len(units)))
+    whole = {}
+    for u in units:
+        whole[u[0]] = whole.get(u[0], 0) + 1
+    seen = {}
+    for i, u in enumerate(mine):
+        out = wl.output(i)
+        if out.size > sample:
+            out = out[np.random.default_rng(u[0]).integers(0, out.size, sample)]
+        name = "%s_op%03d" % (tags[u[0]], u[0])
+        if whole[u[0]] > 1:
+            k = seen.get(u[0], 0)
+            seen[u[0]] = k + 1
+            name += "_r%dp%d" % (rank, k)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(out, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: per-op kernel times "
+                         "(per_set, roofline), the vendor comparator and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write every unit's output of the last step to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample of the larger ones)")
     ap.add_argument("--sets", default=",".join(DEFAULT_SETS))
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow more ranks than GPUs (ranks share devices; the line says shared_device)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
-    ap.add_argument("--per-op", default="", help="write per-unit times (JSON, all ranks) to this path")
+    ap.add_argument("--per-op", default="", help="--full: write per-unit times (JSON, all ranks) to this path")
     ap.add_argument("--eager", action="store_true", help="launch op by op from Python instead of hipGraph replay")
     ap.add_argument("--op-timing", choices=["graph", "events"], default="graph",
                     help="per-op time: amortized over a replayed graph of back-to-back calls (default), or HIP "
@@ -185,6 +226,8 @@ def main():
                     help="also time rocBLAS sgemm / MIOpen conv(+bias+ReLU) per unit (libboda_hip_vendor.so): "
                          "per_set.*.vendor_ms, context only")
     args = ap.parse_args()
+    if args.per_op and not args.full:
+        ap.error("--per-op writes the per-op times, which only --full measures")
 
     dd = Dist()
     if dd.world != args.gpus:
@@ -226,6 +269,47 @@ def main():
     elapsed = dd.max(t1 - t0)
     rank_times = dd.gather_obj(t1 - t0)
 
+    if args.dump_outputs:
+        dump_outputs(wl, mine, units, tags, args.dump_outputs, dd.rank)
+
+    my_flops = sum(s.flops() for s in my_shapes)
+    total_flops = dd.sum(my_flops) * args.steps
+    value = total_flops / elapsed / 1e9
+    n_split = len({u[0] for u in units if u[1] != shapes[u[0]]})
+    line = {
+        "metric": "per-op GFLOPS and % fp32 roofline on sgemm-ops-full + conv-ops (AlexNet/NiN/GoogLeNet)",
+        "metric_note": "value aggregates the three lists of config.workload (the metric's two plus op_sigs_full, "
+                       "BASELINE config C5); per_set (--full) holds each list's own figures",
+        "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": dd.world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic (reference gen_data mode 5, generated on device)",
+        "config": {"workload": " + ".join(SETS[n] for n in set_names) + " (one main-kernel launch per op per step)",
+                   "launch": "eager" if args.eager else "hipGraph replay of each step",
+                   "ops": len(shapes), "units": len(units), "ops_cut_into_panels": n_split,
+                   "panel_operands": "each column panel (M x n_j x K) owns contiguous a (K x M), b (K x n_j) "
+                                     "and c (M x n_j); no strided slice of a shared b",
+                   "gflop_per_step": round(sum(s.flops() for s in shapes) / 1e9, 3),
+                   "parallelism": "op-shard%d (LPT, no collective)" % dd.world,
+                   "lpt_imbalance_predicted": round(pred_imb, 4),
+                   "lpt_imbalance_measured": round(imbalance(rank_times), 4),
+                   "shared_device": shared,
+                   "plat": dev.plat_tag()},
+        "full": args.full,
+    }
+
+    def finish():
+        if dd.rank == 0:
+            print(json.dumps(line), flush=True)
+        for g in graphs:
+            dev.graph_destroy(g)
+        wl.free()
+        dev.close()
+        dd.close()
+
+    if not args.full:  # the plain run ends here: nothing below is needed for the headline
+        return finish()
+
     # Per-op GPU time (the reference's per-op convention, src/rtc_prof.cc:104-124): K more
     # steps, each op timed by HIP events recorded on its own first/last kernel dispatch.
     # With --op-timing graph (default) those are only the estimate that sizes a replayed
@@ -262,10 +346,6 @@ def main():
                 vinfo[i] = vd.time(my_shapes[i], reps)
                 vtime[i] = vinfo[i]["ms"] / 1e3
             vd.close()
-
-    my_flops = sum(s.flops() for s in my_shapes)
-    total_flops = dd.sum(my_flops) * args.steps
-    value = total_flops / elapsed / 1e9
 
     # every rank's per-unit records, gathered on rank 0 (per-set sums and the dominant kernel are
     # over the whole job)
@@ -371,45 +451,17 @@ def main():
                             roofline_frac_executed=r["roof_exec_s"] / r["kernel_s"])
                        for r in recs], f, indent=0)
 
-    if dd.rank == 0:
-        n_split = len({u[0] for u in units if u[1] != shapes[u[0]]})
-        line = {
-            "metric": "per-op GFLOPS and % fp32 roofline on sgemm-ops-full + conv-ops (AlexNet/NiN/GoogLeNet)",
-            "metric_note": "value aggregates the three lists of config.workload (the metric's two plus op_sigs_full, "
-                           "BASELINE config C5); per_set holds each list's own figures",
-            "value": round(value, 2), "unit": "GFLOP/s", "n_gpus": dd.world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic (reference gen_data mode 5, generated on device)",
-            "config": {"workload": " + ".join(SETS[n] for n in set_names) + " (one main-kernel launch per op per step)",
-                       "launch": "eager" if args.eager else "hipGraph replay of each step",
-                       "op_timing": ("per-op amortized time over a replayed hipGraph of back-to-back calls, "
-                                     "HIP events around the replay (after the timed region)"
-                                     if args.op_timing == "graph" else
-                                     "HIP events on each op's first/last kernel dispatch (hipExtLaunchKernel), "
-                                     "K extra eager steps after the timed region"),
-                       "ops": len(shapes), "units": len(units), "ops_cut_into_panels": n_split,
-                       "panel_operands": "each column panel (M x n_j x K) owns contiguous a (K x M), b (K x n_j) "
-                                         "and c (M x n_j); no strided slice of a shared b",
-                       "gflop_per_step": round(sum(s.flops() for s in shapes) / 1e9, 3),
-                       "parallelism": "op-shard%d (LPT, no collective)" % dd.world,
-                       "lpt_imbalance_predicted": round(pred_imb, 4),
-                       "lpt_imbalance_measured": round(imbalance(rank_times), 4),
-                       "shared_device": shared,
-                       "plat": dev.plat_tag(),
-                       "vendor": ("rocblas_sgemm / MIOpen Find-chosen conv fwd + miopenOpTensor bias + "
-                                  "miopenActivationForward ReLU, same units, amortized back-to-back calls, "
-                                  "context only" if args.vendor == "on" and not vendor_note else vendor_note)},
-            "per_set": per_set,
-            "roofline": roof,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(line), flush=True)
-    for g in graphs:
-        dev.graph_destroy(g)
-    wl.free()
-    dev.close()
-    dd.close()
+    line["config"].update({
+        "op_timing": ("per-op amortized time over a replayed hipGraph of back-to-back calls, "
+                      "HIP events around the replay (after the timed region)"
+                      if args.op_timing == "graph" else
+                      "HIP events on each op's first/last kernel dispatch (hipExtLaunchKernel), "
+                      "K extra eager steps after the timed region"),
+        "vendor": ("rocblas_sgemm / MIOpen Find-chosen conv fwd + miopenOpTensor bias + "
+                   "miopenActivationForward ReLU, same units, amortized back-to-back calls, "
+                   "context only" if args.vendor == "on" and not vendor_note else vendor_note)})
+    line.update({"per_set": per_set, "roofline": roof, "cpu_baseline": cpu})
+    finish()
 
 
 if __name__ == "__main__":

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_small_sets_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sets", "sgemm-tiny,sgemm-small", "--steps",
-                        "2", "--warmup", "1", "--no-cpu-baseline", "--vendor", "off"],
+                        "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--vendor", "off"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -27,3 +27,25 @@ def test_bench_small_sets_line():
     cfg = line["config"]
     assert cfg["units"] >= cfg["ops"] and cfg["ops_cut_into_panels"] <= cfg["ops"], cfg
     assert line["roofline"]["peak"] > 0
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """Without --full: the headline keys only (no per-op passes), and --dump-outputs writes one float32
+    array per unit, a fixed sample of the larger ones."""
+    import numpy as np
+    out = tmp_path / "outs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sets", "sgemm-tiny,sgemm-small",
+                        "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["full"] is False
+    assert "per_set" not in line and "roofline" not in line and "cpu_baseline" not in line
+    files = sorted(out.glob("*.npy"))
+    assert len(files) == line["config"]["units"]
+    arrs = [np.load(f) for f in files]
+    assert all(a.dtype == np.float32 and a.ndim == 1 and a.size > 0 and np.isfinite(a).all() for a in arrs)
+    assert any(np.abs(a).max() > 0 for a in arrs)
+    assert sum(f.stat().st_size for f in files) <= 64 * 1000 * 1000

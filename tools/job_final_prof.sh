@@ -9,5 +9,5 @@ tools/gpu_job.sh \
   gputests 1000 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread :: \
   smoke 120 python -u -c "import __graft_entry__ as g; g.smoke()" :: \
   profgraph 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_graph -o bench -- \
-    python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --vendor off --op-timing events \
+    python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --vendor off --op-timing events \
     --per-op gpurun_out/bench_perop_prof.json

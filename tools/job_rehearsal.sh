@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-  --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --rehearsal --no-cpu-baseline --vendor off \
+  --master-port 29517 bench.py --full --gpus 2 --steps 2 --warmup 1 --rehearsal --no-cpu-baseline --vendor off \
   > gpurun_out/rehearsal.log 2>&1; rc=$?
 grep '"metric"' gpurun_out/rehearsal.log | tail -1 > gpurun_out/rehearsal_line.json
 tail -3 gpurun_out/rehearsal.log | cut -c1-300

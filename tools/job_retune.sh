@@ -15,6 +15,7 @@ echo "tune rc=$rc"; tail -3 gpurun_out/tune_rt.log
 [ $rc -eq 0 ] || [ $rc -eq 124 ] || exit $rc
 if [ "${BENCH:-0}" = 1 ]; then
   timeout -k 10 300 env BH_TUNE_FILE=gpurun_out/tune.out python -u bench.py --sets conv,op-sigs --steps 3 --warmup 1 \
+    --full \
     --vendor off --no-cpu-baseline --per-op gpurun_out/perop_rt.json > gpurun_out/bench_rt.log 2>&1 || exit $?
   tail -1 gpurun_out/bench_rt.log | cut -c1-300
 fi

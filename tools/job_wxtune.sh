@@ -12,6 +12,7 @@ tools/gpu_job.sh \
     --key-re '^conv \d+ \d+ \d+ \d+ \d+ (3 3 1 1 [01] [01]|5 5 1 1 [012] [012])$' \
     --merge --out gpurun_out/tune.out --json gpurun_out/tune_wx.json :: \
   bench 400 env BH_TUNE_FILE=gpurun_out/tune.out python -u bench.py --sets conv,op-sigs --steps 3 --warmup 1 --vendor off \
+    --full \
     --no-cpu-baseline --per-op gpurun_out/perop_wx.json :: \
   pmck1s 400 tools/pmc.sh gpurun_out/pmck1s python3 tools/profile_op.py conv 20,96,54,54,96,1,1,1,1,0,0 --iters 20 :: \
   pmcwx 400 env BH_TUNE_FILE=gpurun_out/tune.out tools/pmc.sh gpurun_out/pmcwx python3 tools/profile_op.py conv 20,64,56,56,192,3,3,1,1,1,1 --iters 20
