@@ -30,7 +30,10 @@ EXPORTS = ["bh_abi_version", "bh_last_error", "bh_device_count", "bh_init", "bh_
            "bh_lrn_fwd_nchw", "bh_relu_inplace", "bh_dropout_inplace", "bh_softmax_chans", "bh_chan_copy", "bh_chan_affine",
            "bh_eltwise", "bh_conv2d_fwd_nchw_slab", "bh_conv2d_fwd_nchw_res", "bh_jit_build", "bh_jit_compile",
            "bh_jit_launch", "bh_jit_release", "bh_conv_filts_packed_floats_banks", "bh_conv_filts_pack_banks",
-           "bh_conv_route_banks", "bh_conv2d_fwd_nchw_pkb"]
+           "bh_conv_route_banks", "bh_conv2d_fwd_nchw_pkb", "bh_conv_bck_filts_packed_floats",
+           "bh_conv_bck_filts_pack", "bh_conv2d_bck_in_nchw", "bh_conv2d_bck_filts_nchw", "bh_conv2d_bck_biases",
+           "bh_conv2d_bck_nchw"]
+GEN_BCK_OUT_GRAD = 5
 BANK_W23, BANK_W43, BANK_W25, BANKS_ALL = 1, 2, 4, 0xffffffff
 
 
@@ -86,6 +89,13 @@ def lib():
         L.bh_conv_filts_pack_banks.argtypes = [c_vp, c_vp, c_vp] + [c_u32] * 5
         L.bh_conv_route_banks.argtypes = [c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]
         L.bh_conv2d_fwd_nchw_pkb.argtypes = [c_vp, c_vp, c_vp, c_vp, c_u32, c_vp, c_vp, c_vp] + [c_u32] * 13 + [ctypes.c_int]
+        L.bh_conv_bck_filts_packed_floats.argtypes = [c_u32] * 4
+        L.bh_conv_bck_filts_packed_floats.restype = ctypes.c_size_t
+        L.bh_conv_bck_filts_pack.argtypes = [c_vp, c_vp, c_vp] + [c_u32] * 4
+        L.bh_conv2d_bck_in_nchw.argtypes = [c_vp] * 5 + [c_u32] * 11
+        L.bh_conv2d_bck_filts_nchw.argtypes = [c_vp] * 4 + [c_u32] * 11
+        L.bh_conv2d_bck_biases.argtypes = [c_vp] * 3 + [c_u32] * 4
+        L.bh_conv2d_bck_nchw.argtypes = [c_vp] * 8 + [c_u32] * 11
         L.bh_pool_out_size.argtypes = [c_u32] * 4
         L.bh_pool_fwd_nchw.argtypes = [c_vp, c_vp, c_vp, c_vp] + [c_u32] * 10 + [ctypes.c_int]
         L.bh_lrn_fwd_nchw.argtypes = [c_vp, c_vp, c_vp, c_vp] + [c_u32] * 5 + [ctypes.c_float] * 3
@@ -139,6 +149,12 @@ def conv_filts_packed_floats(s, banks=None):
     if banks is None:
         return lib().bh_conv_filts_packed_floats(s.OC, s.IC, s.KY, s.KX)
     return lib().bh_conv_filts_packed_floats_banks(s.OC, s.IC, s.KY, s.KX, banks)
+
+
+def conv_bck_filts_packed_floats(s):
+    """Floats of the bck pack of conv shape s (bh_conv_bck_filts_pack): the transposed-flipped bank
+    followed by its forward pack."""
+    return lib().bh_conv_bck_filts_packed_floats(s.OC, s.IC, s.KY, s.KX)
 
 
 def pool_out_size(n, k, stride, pad):
@@ -361,6 +377,27 @@ class Device:
             _check(lib().bh_conv_filts_pack(self.ctx, filts.ptr, packed.ptr, s.OC, s.IC, s.KY, s.KX))
         else:
             _check(lib().bh_conv_filts_pack_banks(self.ctx, filts.ptr, packed.ptr, s.OC, s.IC, s.KY, s.KX, banks))
+
+    # ---- backward conv (bh_bck.hip); s is the forward op's shape, og = out_grad_loss B x OC x OH x OW
+    def conv_bck_filts_pack(self, filts, packed, s):
+        """The bck pack (conv_bck_filts_packed_floats(s) floats): made once, untimed, like conv_filts_pack."""
+        _check(lib().bh_conv_bck_filts_pack(self.ctx, filts.ptr, packed.ptr, s.OC, s.IC, s.KY, s.KX))
+
+    def conv_bck_in(self, filts, og, in_grad, s, packed=None):
+        _check(lib().bh_conv2d_bck_in_nchw(self.ctx, filts.ptr, packed.ptr if packed is not None else None, og.ptr,
+                                           in_grad.ptr, *s.as_dims()))
+
+    def conv_bck_filts(self, inp, og, filts_grad, s):
+        _check(lib().bh_conv2d_bck_filts_nchw(self.ctx, inp.ptr, og.ptr, filts_grad.ptr, *s.as_dims()))
+
+    def conv_bck_biases(self, og, biases_grad, s):
+        _check(lib().bh_conv2d_bck_biases(self.ctx, og.ptr, biases_grad.ptr, s.B, s.OC, s.OH, s.OW))
+
+    def conv_bck(self, inp, filts, og, in_grad, filts_grad, biases_grad, s, packed=None):
+        """bh_conv2d_bck_nchw: the three gradients as one call; in_grad may be None."""
+        _check(lib().bh_conv2d_bck_nchw(self.ctx, inp.ptr, filts.ptr, packed.ptr if packed is not None else None,
+                                        og.ptr, in_grad.ptr if in_grad is not None else None, filts_grad.ptr,
+                                        biases_grad.ptr, *s.as_dims()))
 
     def route_banks(self, s):
         """The Winograd bank mask the route of conv shape s on this context reads (0: k-major only)."""

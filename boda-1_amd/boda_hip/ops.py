@@ -216,6 +216,43 @@ def conv_shape(op):
     return s
 
 
+def bck_conv_shape(op):
+    """Op (type BckConv, src/conv_util.cc:65) -> the ConvShape of its forward op, checking that
+    in_grad_loss / filts_grad_loss / biases_grad_loss have the dims of in / filts / biases and that
+    out_grad_loss is B x OC x OH x OW of conv_in_sz_to_out_sz."""
+    if op.type != "BckConv":
+        raise ValueError("not a BckConv op: %s" % op.type)
+    for n in ("in", "filts", "biases", "out_grad_loss", "kern_sz", "stride", "in_pad"):
+        if n not in op.dims:
+            raise ValueError("BckConv op without %s dims: %s" % (n, op.line))
+    din, df = op.dims["in"], op.dims["filts"]
+    ks, st, pd = op.dims["kern_sz"], op.dims["stride"], op.dims["in_pad"]
+    s = ConvShape(B=din["img"], IC=din["chan"], H=din["y"], W=din["x"], OC=df["out_chan"],
+                  KY=ks["y"], KX=ks["x"], sy=st["y"], sx=st["x"], py=pd["y"], px=pd["x"])
+    if df["in_chan"] != s.IC or df["y"] != s.KY or df["x"] != s.KX:
+        raise ValueError("filts dims inconsistent with in / kern_sz: %s" % op.line)
+    if list(op.dims["biases"].values()) != [s.OC]:
+        raise ValueError("biases dims inconsistent with filts: %s" % op.line)
+    for g, v in (("in_grad_loss", "in"), ("filts_grad_loss", "filts"), ("biases_grad_loss", "biases")):
+        if g in op.dims and list(op.dims[g].items()) != list(op.dims[v].items()):
+            raise ValueError("%s dims differ from %s: %s" % (g, v, op.line))
+    do = op.dims["out_grad_loss"]
+    if (do["img"], do["chan"], do["y"], do["x"]) != (s.B, s.OC, s.OH, s.OW):
+        raise ValueError("out_grad_loss dims inconsistent with conv_in_sz_to_out_sz: %s" % op.line)
+    return s
+
+
+def bck_flops(s):
+    """BckConv work model (the reference gives none, src/cnn_op.cc:330): the input and the filter
+    gradient each do the forward's M*N*K multiply-adds, the bias gradient M*N adds."""
+    return 4 * s.M * s.N * s.K + s.M * s.N
+
+
+def bck_bytes(s):
+    """in and filts read, in_grad and filts_grad written, out_grad read, biases_grad written."""
+    return 4 * (2 * s.B * s.IC * s.H * s.W + 2 * s.OC * s.K + s.B * s.OC * s.OH * s.OW + s.OC)
+
+
 def sgemm_shape(op):
     if op.type != "sgemm":
         raise ValueError("not an sgemm op: %s" % op.type)
@@ -243,4 +280,6 @@ def read_ops(path, types=("Convolution", "sgemm")):
 
 
 def shape_of(op):
+    if op.type == "BckConv":
+        return bck_conv_shape(op)
     return conv_shape(op) if op.type == "Convolution" else sgemm_shape(op)

@@ -32,6 +32,12 @@ struct bh_ctx {
   uint64_t cnt_n = 0;
   void *wpack = nullptr;  // k-major filter bank for the ring conv kernels, grown on demand
   size_t wpack_bytes = 0;
+  // backward conv (bh_bck.hip): overrides of op 2 (input gradient) / op 3 (filter gradient), and the
+  // bck pack (transposed-flipped bank + its forward pack) of a call that was given none
+  int bck_cfg[2] = {-1, -1};
+  int bck_splits[2] = {0, 0};
+  void *bckw = nullptr;
+  size_t bckw_bytes = 0;
   // outgrown workspaces still referenced by captured graphs: freed with the last graph (or the context)
   // (a graph replays the pointers it was captured with)
   std::vector<void *> retired;
@@ -152,4 +158,13 @@ std::string conv_variant_ctx(bh_ctx *ctx, const uint32_t *d);
 int tune_set(bh_ctx *ctx, int op, int cfg, int splits);
 int tune_cfg_name(int op, int cfg, std::string &out);
 void jit_release_all(bh_ctx *c);
+// backward conv (bh_bck.hip); d = B,IC,H,W,OC,KY,KX,sy,sx,py,px of the forward op
+size_t bck_filts_packed_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX);
+int launch_bck_filts_pack(bh_ctx *ctx, const float *filts, float *packed, uint32_t OC, uint32_t IC, uint32_t KY,
+                          uint32_t KX, bool first, bool last);
+int launch_bck(bh_ctx *ctx, const float *in, const float *filts, const float *packed, const float *out_grad,
+               float *in_grad, float *filts_grad, float *biases_grad, const uint32_t *d);
+std::string bck_variant(bh_ctx *ctx, int op, const uint32_t *d);  // op 2 / 3; ctx may be null
+int bck_tune_set(bh_ctx *ctx, int op, int cfg, int splits);
+int bck_tune_cfg_name(int op, int cfg, std::string &out);
 }  // namespace bh

@@ -55,10 +55,12 @@ __device__ __forceinline__ float gen_one(const gen_args &g, uint64_t i) {
       break;
     }
     case BH_GEN_CONV_IN:
+    case BH_GEN_BCK_OUT_GRAD:
     case BH_GEN_CONV_FILTS: {  // img:chan:y:x / out_chan:in_chan:y:x
       uint32_t X = g.d[3], Y = g.d[2];
       uint32_t x = (uint32_t)(i % X), y = (uint32_t)((i / X) % Y);
-      uint32_t seed = g.kind == BH_GEN_CONV_IN ? 234234567u : 8753985u;
+      // out_grad_loss: gen_data_Convolution_in's modes with a seed of its own
+      uint32_t seed = g.kind == BH_GEN_CONV_IN ? 234234567u : (g.kind == BH_GEN_BCK_OUT_GRAD ? 51283747u : 8753985u);
       if (mode == 2) v += (float)x;
       if (mode == 3) v += (float)y;
       else if (mode == 4) { if (x == X / 2 && y == Y / 2) v += 1.0f; }
@@ -106,6 +108,7 @@ int launch_gen_data(bh_ctx *ctx, int kind, float *dst, const uint32_t dims[4], u
       g.n = (uint64_t)dims[0] * dims[1];
       break;
     case BH_GEN_CONV_IN:
+    case BH_GEN_BCK_OUT_GRAD:
     case BH_GEN_CONV_FILTS:
       for (int i = 0; i < 4; ++i) g.d[i] = dims[i];
       g.n = (uint64_t)dims[0] * dims[1] * dims[2] * dims[3];

@@ -134,6 +134,7 @@ int bh_destroy(bh_ctx *c) {
   for (void *r : c->retired) (void)hipFree(r);
   if (c->ws) (void)hipFree(c->ws);
   if (c->wpack) (void)hipFree(c->wpack);
+  if (c->bckw) (void)hipFree(c->bckw);
   if (c->stamps) (void)hipFree(c->stamps);
   if (c->cnt) (void)hipFree(c->cnt);
   (void)hipStreamDestroy(c->stream);
@@ -411,6 +412,68 @@ int bh_conv_filts_pack_banks(bh_ctx *c, const float *filts, float *packed, uint3
   return bh::launch_conv_filts_pack(c, filts, packed, OC, IC, KY, KX, banks);
 }
 
+size_t bh_conv_bck_filts_packed_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX) {
+  return bh::bck_filts_packed_floats(OC, IC, KY, KX);
+}
+
+int bh_conv_bck_filts_pack(bh_ctx *c, const float *filts, float *packed, uint32_t OC, uint32_t IC, uint32_t KY,
+                           uint32_t KX) {
+  BH_ENTER_CALL(c);
+  if (!filts || !packed) return bh::fail(BH_ERR, "null tensor");
+  if (!OC || !IC || !KY || !KX) return bh::fail(BH_ERR, "conv_bck_filts_pack: zero-sized dimension");
+  return bh::launch_bck_filts_pack(c, filts, packed, OC, IC, KY, KX, true, true);
+}
+
+// dims of a backward conv are consistent: no zero extent, the padded input holds a window
+static int bck_check_dims(const uint32_t *d) {
+  for (int i = 0; i < 9; ++i)
+    if (!d[i]) return bh::fail(BH_ERR, "bck conv: zero-sized dimension or stride");
+  if ((uint64_t)d[2] + 2ull * d[9] < d[5] || (uint64_t)d[3] + 2ull * d[10] < d[6])
+    return bh::fail(BH_ERR, "bck conv: padded input smaller than kernel");
+  return BH_OK;
+}
+
+int bh_conv2d_bck_nchw(bh_ctx *c, const float *in, const float *filts, const float *packed, const float *out_grad,
+                       float *in_grad, float *filts_grad, float *biases_grad, uint32_t B, uint32_t IC, uint32_t H,
+                       uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py,
+                       uint32_t px) {
+  BH_ENTER_CALL(c);
+  if (!in || !filts || !out_grad || !filts_grad || !biases_grad) return bh::fail(BH_ERR, "null tensor");
+  const uint32_t d[11] = {B, IC, H, W, OC, KY, KX, sy, sx, py, px};
+  if (int rc = bck_check_dims(d)) return rc;
+  return bh::launch_bck(c, in, filts, packed, out_grad, in_grad, filts_grad, biases_grad, d);
+}
+
+int bh_conv2d_bck_in_nchw(bh_ctx *c, const float *filts, const float *packed, const float *out_grad, float *in_grad,
+                          uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX,
+                          uint32_t sy, uint32_t sx, uint32_t py, uint32_t px) {
+  BH_ENTER_CALL(c);
+  if (!filts || !out_grad || !in_grad) return bh::fail(BH_ERR, "null tensor");
+  const uint32_t d[11] = {B, IC, H, W, OC, KY, KX, sy, sx, py, px};
+  if (int rc = bck_check_dims(d)) return rc;
+  return bh::launch_bck(c, nullptr, filts, packed, out_grad, in_grad, nullptr, nullptr, d);
+}
+
+int bh_conv2d_bck_filts_nchw(bh_ctx *c, const float *in, const float *out_grad, float *filts_grad, uint32_t B,
+                             uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX, uint32_t sy,
+                             uint32_t sx, uint32_t py, uint32_t px) {
+  BH_ENTER_CALL(c);
+  if (!in || !out_grad || !filts_grad) return bh::fail(BH_ERR, "null tensor");
+  const uint32_t d[11] = {B, IC, H, W, OC, KY, KX, sy, sx, py, px};
+  if (int rc = bck_check_dims(d)) return rc;
+  return bh::launch_bck(c, in, nullptr, nullptr, out_grad, nullptr, filts_grad, nullptr, d);
+}
+
+int bh_conv2d_bck_biases(bh_ctx *c, const float *out_grad, float *biases_grad, uint32_t B, uint32_t OC, uint32_t OH,
+                         uint32_t OW) {
+  BH_ENTER_CALL(c);
+  if (!out_grad || !biases_grad) return bh::fail(BH_ERR, "null tensor");
+  if (!B || !OC || !OH || !OW) return bh::fail(BH_ERR, "bck conv: zero-sized dimension");
+  // a 1x1 stride-1 op of one input channel has exactly this out_grad
+  const uint32_t d[11] = {B, 1, OH, OW, OC, 1, 1, 1, 1, 0, 0};
+  return bh::launch_bck(c, nullptr, nullptr, nullptr, out_grad, nullptr, nullptr, biases_grad, d);
+}
+
 int bh_conv_route_banks(bh_ctx *c, const uint32_t *dims, uint32_t *banks) {
   // c may be NULL: the tuning table's / heuristic's route (no device needed)
   if (!dims || !banks) return bh::fail(BH_ERR, "null argument");
@@ -423,6 +486,7 @@ int bh_variant_name(int op, const uint32_t *dims, char *buf, size_t n) {
   std::string s;
   if (op == 0) s = bh::sgemm_variant(dims[0], dims[1], dims[2]);
   else if (op == 1) s = bh::conv_variant(dims);
+  else if (op == 2 || op == 3) s = bh::bck_variant(nullptr, op, dims);
   else return bh::fail(BH_ERR, "unknown op kind");
   std::snprintf(buf, n, "%s", s.c_str());
   return BH_OK;
@@ -434,6 +498,7 @@ int bh_variant_name_ctx(bh_ctx *c, int op, const uint32_t *dims, char *buf, size
   std::string s;
   if (op == 0) s = bh::sgemm_variant_ctx(c, dims[0], dims[1], dims[2]);
   else if (op == 1) s = bh::conv_variant_ctx(c, dims);
+  else if (op == 2 || op == 3) s = bh::bck_variant(c, op, dims);
   else return bh::fail(BH_ERR, "unknown op kind");
   std::snprintf(buf, n, "%s", s.c_str());
   return BH_OK;
@@ -513,6 +578,7 @@ int bh_graph_destroy(bh_ctx *c, int graph_id) {
 
 int bh_tune_set(bh_ctx *c, int op, int cfg_index, int splits) {
   BH_ENTER(c);
+  if (op == 2 || op == 3) return bh::bck_tune_set(c, op, cfg_index, splits);
   return bh::tune_set(c, op, cfg_index, splits);
 }
 
@@ -524,7 +590,7 @@ int bh_tune_set_policy(bh_ctx *c, int op, int wt) {
 int bh_tune_cfg_name(int op, int cfg_index, char *buf, size_t n) {
   if (!buf || !n) return bh::fail(BH_ERR, "null buffer");
   std::string s;
-  int rc = bh::tune_cfg_name(op, cfg_index, s);
+  int rc = (op == 2 || op == 3) ? bh::bck_tune_cfg_name(op, cfg_index, s) : bh::tune_cfg_name(op, cfg_index, s);
   if (rc == BH_OK) std::snprintf(buf, n, "%s", s.c_str());
   return rc;
 }

@@ -151,7 +151,11 @@ struct hip_compute_t : public rtc_compute_t {
   void compile(std::vector<rtc_func_info_t> const &fis, rtc_compile_opts_t const &opts) override {
     static const std::set<std::string> kinds = {"hip_sgemm", "hip_conv",  "hip_xpose_filts", "hip_pool",
                                                 "hip_lrn",   "hip_relu",  "hip_copy",        "hip_affine",
-                                                "hip_eltwise", "hip_softmax", "hip_dropout"};
+                                                "hip_eltwise", "hip_softmax", "hip_dropout",
+                                                // BckConv: the combined call (ops-prof), the three calls Boda's
+                                                // conv_pipe_fwd_t emits (src/rtc_fwd.cc:378-400), the bck pack
+                                                "hip_bck_conv", "hip_bck_in", "hip_bck_filts", "hip_bck_biases",
+                                                "hip_bck_xpose_filts"};
     std::string src = cucl_hip_prelude;
     std::vector<std::string> jit_names;
     for (auto const &fi : fis) {
@@ -238,6 +242,33 @@ struct hip_compute_t : public rtc_compute_t {
     ~tune_guard_t() {
       if (cfg) (void)bh_tune_set(ctx, op, -1, 0);
       if (wt) (void)bh_tune_set_policy(ctx, op, -1);
+    }
+  };
+  // a BckConv op's tune on op 2 (input gradient) and op 3 (filter gradient): a cfg name only one of
+  // them has applies to that one; ref64 is a configuration of both (and, through op 3, of the bias sum)
+  struct bck_tune_guard_t {
+    bh_ctx *ctx;
+    bool set[2] = {false, false};
+    bck_tune_guard_t(bh_ctx *c, op_base_t const &fop) : ctx(c) {
+      auto cf = fop.str_vals.find("hip_cfg"), sp = fop.str_vals.find("hip_splits");
+      if (cf == fop.str_vals.end()) {
+        if (sp != fop.str_vals.end()) rt_err("op_tune: splits without cfg");
+        return;
+      }
+      const int splits = sp == fop.str_vals.end() ? 0 : parse_i32(sp->second, "splits");
+      for (int op = 2; op <= 3; ++op) {
+        char buf[128];
+        for (int i = 0; bh_tune_cfg_name(op, i, buf, sizeof buf) == BH_OK; ++i)
+          if (cf->second == buf) {
+            bh_check(bh_tune_set(ctx, op, i, op == 3 ? splits : 0), "bh_tune_set");
+            set[op - 2] = true;
+          }
+      }
+      if (!set[0] && !set[1]) unsup_err("op_tune: no bck conv configuration named '" + cf->second + "'");
+    }
+    ~bck_tune_guard_t() {
+      for (int op = 2; op <= 3; ++op)
+        if (set[op - 2]) (void)bh_tune_set(ctx, op, -1, 0);
     }
   };
   // the Winograd banks a pack of this op holds (op str_vals hip_pack_banks, a BH_BANK_* mask;
@@ -392,8 +423,45 @@ struct hip_compute_t : public rtc_compute_t {
       bh_check(bh_conv_filts_pack_banks(ctx, arg_ptr(rfc, "filts"), arg_ptr(rfc, "filts_xp"), s.OC, s.IC, s.KY, s.KX,
                                         banks),
                "hip_xpose_filts");
+    } else if (kind == "hip_bck_conv" || kind == "hip_bck_in" || kind == "hip_bck_filts" || kind == "hip_bck_biases") {
+      // arg names: those of test/rtc/BckConv_{in,filts,biases}_grad_loss.cucl (stride / in_pad are REF
+      // args there: the geometry comes from the op); filts_xp (optional): the bck pack
+      conv_shape_t s = get_bck_conv_shape(fi.op);
+      bck_tune_guard_t tg(ctx, fi.op);
+      const uint32_t d[11] = {s.B, s.IC, s.H, s.W, s.OC, s.KY, s.KX, s.sy, s.sx, s.py, s.px};
+      if (kind == "hip_bck_conv") {
+        ev.variant = variant_of(2, d) + "+" + variant_of(3, d);
+        bh_check(bh_conv2d_bck_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "filts"), arg_ptr(rfc, "filts_xp", true),
+                                    arg_ptr(rfc, "out_grad_loss"), arg_ptr(rfc, "in_grad_loss", true),
+                                    arg_ptr(rfc, "filts_grad_loss"), arg_ptr(rfc, "biases_grad_loss"), s.B, s.IC, s.H,
+                                    s.W, s.OC, s.KY, s.KX, s.sy, s.sx, s.py, s.px),
+                 fn);
+      } else if (kind == "hip_bck_in") {
+        ev.variant = variant_of(2, d);
+        bh_check(bh_conv2d_bck_in_nchw(ctx, arg_ptr(rfc, "filts"), arg_ptr(rfc, "filts_xp", true),
+                                       arg_ptr(rfc, "out_grad_loss"), arg_ptr(rfc, "in_grad_loss"), s.B, s.IC, s.H, s.W,
+                                       s.OC, s.KY, s.KX, s.sy, s.sx, s.py, s.px),
+                 fn);
+      } else if (kind == "hip_bck_filts") {
+        ev.variant = variant_of(3, d);
+        bh_check(bh_conv2d_bck_filts_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out_grad_loss"),
+                                          arg_ptr(rfc, "filts_grad_loss"), s.B, s.IC, s.H, s.W, s.OC, s.KY, s.KX, s.sy,
+                                          s.sx, s.py, s.px),
+                 fn);
+      } else {
+        bh_check(bh_conv2d_bck_biases(ctx, arg_ptr(rfc, "out_grad_loss"), arg_ptr(rfc, "biases_grad_loss"), s.B, s.OC,
+                                      s.OH, s.OW),
+                 fn);
+      }
+    } else if (kind == "hip_bck_xpose_filts") {  // the bck pack, once per filts var before the timed calls
+      conv_shape_t s = get_bck_conv_shape(fi.op);
+      if (arg_dims(rfc, "filts_xp").elems() != bh_conv_bck_filts_packed_floats(s.OC, s.IC, s.KY, s.KX))
+        rt_err("hip_bck_xpose_filts: filts_xp has the wrong size");
+      bh_check(bh_conv_bck_filts_pack(ctx, arg_ptr(rfc, "filts"), arg_ptr(rfc, "filts_xp"), s.OC, s.IC, s.KY, s.KX),
+               "hip_bck_xpose_filts");
     } else {  // gen_data_<type>_<arg>
       std::string an = fn.substr(fn.rfind('_') + 1);
+      if (fn == "gen_data_BckConv_out_grad_loss") an = "out_grad_loss";
       uint32_t mode = (uint32_t)arg_val(rfc, "mode", 5);
       float vi = (float)arg_val(rfc, "vi", 0.0);
       dims_t const &d = arg_dims(rfc, an);
@@ -404,6 +472,10 @@ struct hip_compute_t : public rtc_compute_t {
       else if (fn == "gen_data_Convolution_in") kind = BH_GEN_CONV_IN;
       else if (fn == "gen_data_Convolution_filts") kind = BH_GEN_CONV_FILTS;
       else if (fn == "gen_data_Convolution_biases") kind = BH_GEN_CONV_BIASES;
+      else if (fn == "gen_data_BckConv_in") kind = BH_GEN_CONV_IN;
+      else if (fn == "gen_data_BckConv_filts") kind = BH_GEN_CONV_FILTS;
+      else if (fn == "gen_data_BckConv_biases") kind = BH_GEN_CONV_BIASES;
+      else if (fn == "gen_data_BckConv_out_grad_loss") kind = BH_GEN_BCK_OUT_GRAD;
       else unsup_err("no gen_data generator '" + fn + "'");
       if (d.d.size() > 4) rt_err("gen_data: too many dims");
       for (size_t i = 0; i < d.d.size(); ++i) dd[i] = d.d[i].sz;

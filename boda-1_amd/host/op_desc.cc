@@ -130,6 +130,30 @@ conv_shape_t get_conv_shape(op_base_t const &op) {
   return s;
 }
 
+conv_shape_t get_bck_conv_shape(op_base_t const &op) {
+  if (op.type != "BckConv") rt_err("not a BckConv op: " + op.type);
+  dims_t const &in = op.get_dims("in"), &f = op.get_dims("filts"), &b = op.get_dims("biases");
+  dims_t const &ks = op.get_dims("kern_sz"), &st = op.get_dims("stride"), &pd = op.get_dims("in_pad");
+  conv_shape_t s;
+  s.B = in.dsz("img"); s.IC = in.dsz("chan"); s.H = in.dsz("y"); s.W = in.dsz("x");
+  s.OC = f.dsz("out_chan"); s.KY = ks.dsz("y"); s.KX = ks.dsz("x");
+  s.sy = st.dsz("y"); s.sx = st.dsz("x"); s.py = pd.dsz("y"); s.px = pd.dsz("x");
+  s.OH = conv_in_sz_to_out_sz(s.H, s.py, s.KY, s.sy);
+  s.OW = conv_in_sz_to_out_sz(s.W, s.px, s.KX, s.sx);
+  if (f.dsz("in_chan") != s.IC || f.dsz("y") != s.KY || f.dsz("x") != s.KX)
+    rt_err("filts dims inconsistent with in / kern_sz: " + op.line);
+  if (b.d.size() != 1 || b.d[0].sz != s.OC) rt_err("biases dims inconsistent with filts: " + op.line);
+  // each gradient has the dims of the var it is the gradient of
+  for (auto const &gv : {std::make_pair("in_grad_loss", "in"), std::make_pair("filts_grad_loss", "filts"),
+                         std::make_pair("biases_grad_loss", "biases")})
+    if (op.has_dims(gv.first) && op.get_dims(gv.first).str() != op.get_dims(gv.second).str())
+      rt_err(std::string(gv.first) + " dims differ from " + gv.second + ": " + op.line);
+  dims_t const &o = op.get_dims("out_grad_loss");
+  if (o.dsz("img") != s.B || o.dsz("chan") != s.OC || o.dsz("y") != s.OH || o.dsz("x") != s.OW)
+    rt_err("out_grad_loss dims inconsistent with conv_in_sz_to_out_sz: " + op.line);
+  return s;
+}
+
 sgemm_shape_t get_sgemm_shape(op_base_t const &op) {
   if (op.type != "sgemm") rt_err("not an sgemm op: " + op.type);
   dims_t const &a = op.get_dims("a"), &b = op.get_dims("b"), &c = op.get_dims("c");
@@ -147,6 +171,14 @@ op_work_t op_work(op_base_t const &op) {
     double M = (double)s.B * s.OH * s.OW, K = (double)s.IC * s.KY * s.KX, N = s.OC;
     w.flops = 2 * M * N * K;
     w.bytes = 4.0 * ((double)s.B * s.IC * s.H * s.W + (double)s.B * s.OC * s.OH * s.OW + N * K + N);
+  } else if (op.type == "BckConv") {
+    // the reference gives BckConv no single value (src/cnn_op.cc:330); ours: the input and the filter
+    // gradient each do the forward's M*N*K multiply-adds, the bias gradient M*N adds; in and filts are
+    // read and their gradients written, out_grad_loss read, biases_grad_loss written
+    conv_shape_t s = get_bck_conv_shape(op);
+    double M = (double)s.B * s.OH * s.OW, K = (double)s.IC * s.KY * s.KX, N = s.OC;
+    w.flops = 4 * M * N * K + M * N;
+    w.bytes = 4.0 * (2.0 * s.B * s.IC * s.H * s.W + 2 * N * K + M * N + N);
   } else if (op.type == "sgemm") {
     sgemm_shape_t s = get_sgemm_shape(op);
     w.flops = 2.0 * s.M * s.N * s.K;
@@ -169,6 +201,17 @@ void add_hip_annotations(op_base_t &op) {
     op.dims_vals["out"] = dims_t({{"img", s.B}, {"chan", s.OC}, {"y", s.OH}, {"x", s.OW}});
     if (op.str_vals.count("conv_has_relu") == 0 && op.scalars.count("conv_has_relu") == 0)
       op.scalars["conv_has_relu"] = 1;  // ops-prof always fuses ReLU (src/cnn_op.cc:335-337)
+    return;
+  }
+  if (op.type == "BckConv") {
+    conv_shape_t s = get_bck_conv_shape(op);
+    op.func_name = "hip_bck_conv";
+    for (char const *n : {"in", "in_grad_loss"})
+      op.dims_vals[n] = dims_t({{"img", s.B}, {"chan", s.IC}, {"y", s.H}, {"x", s.W}});
+    for (char const *n : {"filts", "filts_grad_loss"})
+      op.dims_vals[n] = dims_t({{"out_chan", s.OC}, {"in_chan", s.IC}, {"y", s.KY}, {"x", s.KX}});
+    for (char const *n : {"biases", "biases_grad_loss"}) op.dims_vals[n] = dims_t({{"out_chan", s.OC}});
+    op.dims_vals["out_grad_loss"] = dims_t({{"img", s.B}, {"chan", s.OC}, {"y", s.OH}, {"x", s.OW}});
     return;
   }
   if (op.type == "sgemm") {

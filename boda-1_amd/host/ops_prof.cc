@@ -92,7 +92,7 @@ std::vector<bool> lpt_mine(std::vector<std::string> const &lines, std::string co
   std::vector<std::pair<double, size_t>> cost;
   for (size_t i = 0; i < lines.size(); ++i) {
     op_base_t op = parse_op_line(lines[i]);
-    double c = (op.type == "Convolution" || op.type == "sgemm") ? roofline_secs(op_work(op)) : 0.0;
+    double c = (op.type == "Convolution" || op.type == "sgemm" || op.type == "BckConv") ? roofline_secs(op_work(op)) : 0.0;
     cost.emplace_back(c, i);
   }
   std::stable_sort(cost.begin(), cost.end(), [](auto const &x, auto const &y) { return x.first > y.first; });
@@ -118,14 +118,18 @@ std::vector<std::string> read_lines(std::string const &fn) {
 
 std::vector<std::string> arg_vars(op_base_t const &op) {
   if (op.type == "Convolution") return {"in", "filts", "biases", "out"};
+  if (op.type == "BckConv")
+    return {"in", "filts", "biases", "out_grad_loss", "in_grad_loss", "filts_grad_loss", "biases_grad_loss"};
   return {"a", "b", "c"};
 }
 std::vector<std::string> in_vars(op_base_t const &op) {
   if (op.type == "Convolution") return {"in", "filts", "biases"};
+  if (op.type == "BckConv") return {"in", "filts", "biases", "out_grad_loss"};
   return {"a", "b"};
 }
 std::vector<std::string> out_vars(op_base_t const &op) {
   if (op.type == "Convolution") return {"out"};
+  if (op.type == "BckConv") return {"in_grad_loss", "filts_grad_loss", "biases_grad_loss"};
   return {"c"};
 }
 
@@ -147,9 +151,20 @@ int main(int argc, char **argv) {
     if (o.kv.count("selftest-wisdom")) return selftest_wisdom(o.get("selftest-wisdom"));
     if (o.kv.count("dump-ops")) {  // parse-only: one line per Convolution/sgemm op, no GPU needed
       size_t skipped = 0;
-      for (auto const &op : read_op_list(o.get("dump-ops"), &skipped)) {
+      // --types=T1,T2 (default: Convolution,sgemm): the op types listed, the others counted as skipped
+      std::vector<std::string> types;
+      for (std::string t = o.get("types", "Convolution,sgemm"); !t.empty();) {
+        size_t c = t.find(',');
+        types.push_back(t.substr(0, c));
+        t = c == std::string::npos ? "" : t.substr(c + 1);
+      }
+      for (auto const &op : read_op_list(o.get("dump-ops"), &skipped, types)) {
         op_work_t w = op_work(op);
-        if (op.type == "Convolution") {
+        if (op.type == "BckConv") {
+          conv_shape_t s = get_bck_conv_shape(op);
+          std::printf("BckConv %u %u %u %u %u %u %u %u %u %u %u %.0f %.0f\n", s.B, s.IC, s.H, s.W, s.OC, s.KY, s.KX,
+                      s.sy, s.sx, s.py, s.px, w.flops, w.bytes);
+        } else if (op.type == "Convolution") {
           conv_shape_t s = get_conv_shape(op);
           std::printf("Convolution %u %u %u %u %u %u %u %u %u %u %u %.0f %.0f\n", s.B, s.IC, s.H, s.W, s.OC, s.KY,
                       s.KX, s.sy, s.sx, s.py, s.px, w.flops, w.bytes);
@@ -174,7 +189,7 @@ int main(int argc, char **argv) {
                    "  [--func-mrd-toler='(variant-or-word=toler,...)'] [--wino-mrd-toler=2e-3] [--max-err=10]\n"
                    "  [--gen-data-mode=5] [--run-iter=1] [--mrd-toler=2e-4] [--device=0] [--write-runs=0]\n"
                    "  [--write-kg-digest=1] [--live-mrd-toler=0]\n"
-                   "  [--skip-ops=0] [--shard=k/n] | --selftest-wisdom=F | --dump-ops=F | --list-shard=k/n --ops-fn=F\n";
+                   "  [--skip-ops=0] [--shard=k/n] | --selftest-wisdom=F | --dump-ops=F [--types=T,...] | --list-shard=k/n --ops-fn=F\n";
       return 2;
     }
     const uint32_t mode = parse_u32(o.get("gen-data-mode", "5"), "--gen-data-mode");
@@ -313,6 +328,18 @@ int main(int argc, char **argv) {
             x.arg_map["filts_xp"] = "filts_xp";
             rtc->run(x);
             c.arg_map["filts_xp"] = "filts_xp";
+          } else if (op.type == "BckConv") {
+            // the bck pack (transposed-flipped bank + its forward pack), untimed like xpose_filts
+            conv_shape_t s = get_bck_conv_shape(op);
+            rtc->compile({{"hip_bck_xpose_filts", "", {}, op}}, rtc_compile_opts_t());
+            const uint32_t nxp = (uint32_t)bh_conv_bck_filts_packed_floats(s.OC, s.IC, s.KY, s.KX);
+            rtc->create_var_with_dims("filts_xp", dims_t(std::vector<std::pair<std::string, uint32_t>>{{"x", nxp}}));
+            rtc_func_call_t x;
+            x.rtc_func_name = "hip_bck_xpose_filts";
+            x.arg_map["filts"] = "filts";
+            x.arg_map["filts_xp"] = "filts_xp";
+            rtc->run(x);
+            c.arg_map["filts_xp"] = "filts_xp";
           }
           uint32_t call_id = 0;
           for (uint32_t r = 0; r < run_iter; ++r) call_id = rtc->run(c);
@@ -332,7 +359,7 @@ int main(int argc, char **argv) {
             } catch (rt_exception const &) {
             }
           }
-        if (op.type == "Convolution") {
+        if (op.type == "Convolution" || op.type == "BckConv") {
           try {
             rtc->release_var("filts_xp");
           } catch (rt_exception const &) {

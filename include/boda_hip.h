@@ -113,6 +113,7 @@ int bh_graph_destroy(bh_ctx *ctx, int graph_id);
 #define BH_GEN_CONV_IN 2
 #define BH_GEN_CONV_FILTS 3
 #define BH_GEN_CONV_BIASES 4
+#define BH_GEN_BCK_OUT_GRAD 5 /* out_grad_loss img:chan:y:x d = {B, OC, OH, OW}: BH_GEN_CONV_IN's modes, a seed of its own */
 int bh_gen_data(bh_ctx *ctx, int kind, float *dst, const uint32_t dims[4], uint32_t mode, float vi);
 
 /* ---- the hot path ------------------------------------------------------
@@ -209,6 +210,39 @@ int bh_conv2d_fwd_nchw_pkb(bh_ctx *ctx, const float *in, const float *filts, con
                            uint32_t out_chan_ofs, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC,
                            uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu);
 
+/* ---- backward convolution: Boda's BckConv (coi src/conv_util.cc:65, planned src/cnn_op.cc:80-160,
+ *      emitted as three calls src/rtc_fwd.cc:378-400; test/rtc/BckConv_{in,filts,biases}_grad_loss.cucl).
+ *      With out_grad = out_grad_loss, B x OC x OH x OW:
+ *        in_grad[n][ic][y][x]       = sum over oc, ky, kx with oy*sy + ky - py == y, ox*sx + kx - px == x
+ *                                     (0 <= oy < OH, 0 <= ox < OW) of out_grad[n][oc][oy][ox] * filts[oc][ic][ky][kx]
+ *        filts_grad[oc][ic][ky][kx] = sum over n, oy, ox of out_grad[n][oc][oy][ox]
+ *                                     * in[n][ic][oy*sy+ky-py][ox*sx+kx-px]   (in-image taps only)
+ *        biases_grad[oc]            = sum over n, oy, ox of out_grad[n][oc][oy][ox]
+ *      Every element of every output is written (in_grad pixels no window covers: 0). No activation
+ *      (ReLU's backward is a separate op). Results are deterministic (fixed summation order).
+ *      The bck pack is the bank transposed (oc <-> ic) and flipped in ky, kx -- [IC][OC][KY][KX], padded
+ *      to a multiple of 4 floats -- followed by the forward pack (bh_conv_filts_pack) of it: the
+ *      stride-1 input gradient is the forward conv of out_grad with that bank at pad (KY-1-py, KX-1-px).
+ *      Made once, untimed, like xpose_filts; packed == NULL: the call makes it in a buffer of the
+ *      context (bit-identical, slower). Routes that do not read the pack ignore it. */
+size_t bh_conv_bck_filts_packed_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX);
+int bh_conv_bck_filts_pack(bh_ctx *ctx, const float *filts, float *packed, uint32_t OC, uint32_t IC,
+                           uint32_t KY, uint32_t KX);
+int bh_conv2d_bck_in_nchw(bh_ctx *ctx, const float *filts, const float *packed, const float *out_grad,
+                          float *in_grad, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC,
+                          uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px);
+int bh_conv2d_bck_filts_nchw(bh_ctx *ctx, const float *in, const float *out_grad, float *filts_grad,
+                             uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
+                             uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px);
+int bh_conv2d_bck_biases(bh_ctx *ctx, const float *out_grad, float *biases_grad, uint32_t B, uint32_t OC,
+                         uint32_t OH, uint32_t OW);
+/* all three as ONE call for bh_time_next_call (first dispatch .. last dispatch); in_grad may be NULL
+ * (a first layer needs none), the other two may not */
+int bh_conv2d_bck_nchw(bh_ctx *ctx, const float *in, const float *filts, const float *packed,
+                       const float *out_grad, float *in_grad, float *filts_grad, float *biases_grad,
+                       uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX,
+                       uint32_t sy, uint32_t sx, uint32_t py, uint32_t px);
+
 /* ---- the other forward layers of Boda's net executor (conv_pipe_fwd_t::gen_op,
  *      src/rtc_fwd.cc:263-405), NCHW fp32 ------------------------------------ */
 /* Pooling (test/rtc/pool.cucl; Caffe output size, a partial last window adds an
@@ -267,7 +301,9 @@ int bh_jit_release(bh_ctx *ctx, int module_id);
 
 /* Name of the kernel variant bh_conv2d_fwd_nchw / bh_sgemm_kmajor would run
  * for a shape (op==0: sgemm with dims[0..2] = M,N,K; op==1: conv with
- * dims[0..10] = B,IC,H,W,OC,KY,KX,sy,sx,py,px). */
+ * dims[0..10] = B,IC,H,W,OC,KY,KX,sy,sx,py,px; op==2 / op==3: the input / filter gradient of
+ * that conv: "bck_in_fwd:<forward variant>" for the stride-1 route, "mfma32_bcki_<cfg>",
+ * "mfma32_bckf_<cfg>_s<splits>", "ref64_bck_in_double" / "ref64_bck_filts_double"). */
 int bh_variant_name(int op, const uint32_t *dims, char *buf, size_t buflen);
 /* The same, under ctx's bh_tune_set / bh_tune_set_policy overrides: the variant a call on ctx
  * runs now. ops-prof names each tune's run by it -- the role of the generated function name
@@ -278,7 +314,9 @@ int bh_variant_name_ctx(bh_ctx *ctx, int op, const uint32_t *dims, char *buf, si
  *      src/cnn_op.H:10-31, src/op-tuner.cc). Kernel choice per exact shape comes
  *      from, in order: an override set here, the tuning table
  *      (boda-1_amd/tuning/gfx950.tune next to the library, or $BH_TUNE_FILE),
- *      a built-in heuristic. op: 0 = sgemm, 1 = conv. ---------------------- */
+ *      a built-in heuristic. op: 0 = sgemm, 1 = conv; 2 = bck input gradient, 3 = bck
+ *      filter gradient (override or heuristic only; "ref64" on op 3 also sums the bias
+ *      gradient in double). ------------------------------------------------ */
 /* force tile configuration cfg_index (-1: back to table/heuristic) and K splits
  * for every later call of op on this context: splits 0 = planned, n > 0 = n
  * splits combined in-kernel by each tile's last-arriving block, -n = n splits
