@@ -32,7 +32,7 @@ EXPORTS = ["bh_abi_version", "bh_last_error", "bh_device_count", "bh_init", "bh_
            "bh_jit_launch", "bh_jit_release", "bh_conv_filts_packed_floats_banks", "bh_conv_filts_pack_banks",
            "bh_conv_route_banks", "bh_conv2d_fwd_nchw_pkb", "bh_conv_bck_filts_packed_floats",
            "bh_conv_bck_filts_pack", "bh_conv2d_bck_in_nchw", "bh_conv2d_bck_filts_nchw", "bh_conv2d_bck_biases",
-           "bh_conv2d_bck_nchw"]
+           "bh_conv2d_bck_nchw", "bh_capture_stats", "bh_capture_trace"]
 GEN_BCK_OUT_GRAD = 5
 BANK_W23, BANK_W43, BANK_W25, BANKS_ALL = 1, 2, 4, 0xffffffff
 
@@ -113,6 +113,9 @@ def lib():
         L.bh_stamps_read.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
         L.bh_capture_begin.argtypes = [c_vp]
         L.bh_capture_end.argtypes = [c_vp, ctypes.POINTER(ctypes.c_int)]
+        if hasattr(L, "bh_capture_stats"):  # a BH_LIB_NAME build from before the capture lanes lacks them
+            L.bh_capture_stats.argtypes = [c_vp, ctypes.POINTER(c_u32)]
+            L.bh_capture_trace.argtypes = [c_vp, ctypes.POINTER(c_u32), c_u32, ctypes.POINTER(c_u32)]
         L.bh_graph_launch.argtypes = [c_vp, ctypes.c_int]
         L.bh_graph_destroy.argtypes = [c_vp, ctypes.c_int]
         L.bh_tune_set.argtypes = [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -295,6 +298,20 @@ class Device:
         g = ctypes.c_int(-1)
         _check(lib().bh_capture_end(self.ctx, ctypes.byref(g)))
         return g.value
+
+    def capture_stats(self):
+        """Of the last finished capture: (lanes used, cross-lane edges, joins, ops scheduled)."""
+        out = (c_u32 * 4)()
+        _check(lib().bh_capture_stats(self.ctx, out))
+        return tuple(out)
+
+    def capture_trace(self):
+        """Per scheduled op of the last finished capture, in call order: (lane, wait mask)."""
+        n = c_u32(0)
+        _check(lib().bh_capture_trace(self.ctx, None, 0, ctypes.byref(n)))
+        out = (c_u32 * max(1, n.value))()
+        _check(lib().bh_capture_trace(self.ctx, out, n.value, ctypes.byref(n)))
+        return [(v & 0xff, v >> 8) for v in out[:n.value]]
 
     def graph_launch(self, g):
         _check(lib().bh_graph_launch(self.ctx, g))

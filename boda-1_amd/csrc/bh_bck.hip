@@ -328,7 +328,7 @@ int launch_filts(bh_ctx *ctx, BckArgs &p, const bck_dims &s, bool last) {
   if (tm > 65535 || p.S > 65535) return bh::fail(BH_UNSUP, "bck conv: filter-gradient grid too large");
   int rc = ensure_ws(ctx, (size_t)p.S * p.ocp * p.qp * 4);
   if (rc != BH_OK) return rc;
-  p.ws = (float *)ctx->ws;
+  p.ws = ws_of(ctx);
   const void *k = cfg ? (const void *)bckf_kernel<64, 64> : (const void *)bckf_kernel<32, 32>;
   rc = bh::launch(ctx, k, dim3(tn, tm, p.S), dim3(cfg ? 256 : 64), args, true, false, "bck_filts");
   if (rc != BH_OK) return rc;

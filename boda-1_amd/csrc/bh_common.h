@@ -10,6 +10,36 @@
 #include <string>
 #include <vector>
 #include "boda_hip.h"
+#include "bh_lanes.h"
+
+namespace bh {
+struct op_scope;
+}
+// Capture-time lane scheduler (bh_runtime.hip, DESIGN.md "Capture lanes"). Lane 0 is the context's own
+// stream with the context's own scratch; lanes 1.. are side streams, each with split-K scratch of its own.
+struct bh_lane {
+  hipStream_t stream = nullptr;
+  void *ws = nullptr;  // split-K workspace of ops on this lane
+  size_t ws_bytes = 0;
+  void *cnt = nullptr;  // split-K arrival tickets of ops on this lane
+  uint64_t cnt_n = 0;
+  bool forked = false;  // holds work of the running capture that lane 0 has not joined yet
+};
+struct bh_sched {
+  int lanes = 1;            // BH_CAPTURE_LANES (1: one chain of dependent launches)
+  double narrow_us = 0;     // BH_CAPTURE_NARROW_US: ops with a roofline time below this are spread
+  bool capturing = false;   // between bh_capture_begin and bh_capture_end
+  bh_lane lane[bh_lanes::MAX_LANES];  // [0]: stream / scratch unused (the context's own)
+  std::vector<hipEvent_t> ev;         // timing-disabled events of the forks, joins and cross-lane edges
+  size_t ev_used = 0;
+  bh_lanes::tracker trk;
+  size_t hw_ws = 0;     // high-water marks of the scratch narrow ops asked for in eager calls
+  bh::op_scope *scope = nullptr;  // the hot-path call being issued
+  uint32_t used_mask = 0;
+  uint32_t cur[4] = {0, 0, 0, 0};    // running capture: -, cross-lane edges, joins, ops scoped
+  uint32_t stats[4] = {0, 0, 0, 0};  // last finished capture: lanes used, edges, joins, ops scoped
+  std::vector<uint32_t> cur_trace, trace;  // per scoped op: lane | wait mask << 8
+};
 
 struct bh_ctx {
   int device = 0;
@@ -41,6 +71,7 @@ struct bh_ctx {
   // outgrown workspaces still referenced by captured graphs: freed with the last graph (or the context)
   // (a graph replays the pointers it was captured with)
   std::vector<void *> retired;
+  bh_sched sched;
 };
 
 namespace bh {
@@ -56,6 +87,34 @@ int check_launch(const char *what);
 // event on the kernel's own dispatch (hipExtLaunchKernel).
 int launch(bh_ctx *ctx, const void *kernel, dim3 grid, dim3 block, void **args, bool first, bool last,
            const char *what, uint32_t shmem = 0);
+
+// ---- capture lanes. A hot-path entry (sgemm, forward conv) opens an op_scope naming the bytes it reads
+// and writes and its roofline time. While the context is capturing, the scope's first launch (or scratch
+// request) picks its lane; every kernel of the call then goes to that lane's stream. Launches outside a
+// scope and direct uses of the context's stream join all lanes first (barrier).
+struct op_scope {
+  bh_ctx *c;
+  bh_lanes::access acc;
+  double est_us = 0;
+  bool narrow = false;
+  bool resolved = false;
+  bool pin0 = false;  // must run on lane 0 (it uses a buffer the context holds once)
+  int lane = 0;
+  op_scope(bh_ctx *ctx, double flops, double bytes);
+  ~op_scope() { c->sched.scope = nullptr; }
+  void read(const void *p, uint64_t bytes) {
+    if (p) acc.read((uint64_t)(uintptr_t)p, bytes);
+  }
+  void write(const void *p, uint64_t bytes) {
+    if (p) acc.write((uint64_t)(uintptr_t)p, bytes);
+  }
+};
+int lane_resolve(bh_ctx *ctx, size_t ws_need);  // pick the open scope's lane (no-op outside a capture)
+int barrier(bh_ctx *ctx);                       // join every lane into the context's stream
+// scratch of the lane the open scope runs on (the context's own on lane 0 / outside a scope)
+int lane_ws(bh_ctx *ctx, size_t bytes);
+int lane_cnt(bh_ctx *ctx, uint64_t n);
+int lane_wpack(bh_ctx *ctx, size_t bytes);
 
 // Magic-number unsigned division for 0 <= n < 2^31, 1 <= d < 2^31:
 // q = (umulhi(n, m) + n) >> s.

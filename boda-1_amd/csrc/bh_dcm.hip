@@ -542,8 +542,8 @@ int launch_dcm(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY
   int rc = ensure_ws(ctx, (size_t)2 * G * c.BM * c.BN * 4);  // two tile slabs per block
   if (rc == BH_OK) rc = ensure_cnt(ctx, (size_t)ntile);
   if (rc != BH_OK) return rc;
-  p.ws = (float *)ctx->ws;
-  p.cnt = (uint32_t *)ctx->cnt;
+  p.ws = ws_of(ctx);
+  p.cnt = cnt_of(ctx);
 #ifdef BH_KTRACE
   p.trace = (unsigned long long *)ctx->stamps + 65536;
 #endif

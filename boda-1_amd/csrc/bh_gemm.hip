@@ -817,17 +817,11 @@ void set_fd(uint32_t d, uint32_t &m, uint32_t &s) {
 }  // namespace
 
 namespace bhk {
-int ensure_ws(bh_ctx *ctx, size_t bytes) {
-  return bh::grow_buffer(ctx, ctx->ws, ctx->ws_bytes, bytes, false, "split-K workspace");
-}
+// (of the lane the call runs on: bh_runtime.hip, capture lanes)
+int ensure_ws(bh_ctx *ctx, size_t bytes) { return bh::lane_ws(ctx, bytes); }
 
 // split-K arrival tickets: zeroed at allocation, reset by each tile's last arriver
-int ensure_cnt(bh_ctx *ctx, uint64_t n) {
-  size_t have = ctx->cnt_n * 4;
-  int rc = bh::grow_buffer(ctx, ctx->cnt, have, std::max<uint64_t>(n, 4096) * 4, true, "split-K tickets");
-  ctx->cnt_n = have / 4;
-  return rc;
-}
+int ensure_cnt(bh_ctx *ctx, uint64_t n) { return bh::lane_cnt(ctx, n); }
 }  // namespace bhk
 
 namespace {
@@ -983,8 +977,8 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
       int rc = ensure_ws(ctx, (size_t)S * nblk * c.BM * c.BN * 4);
       if (rc == BH_OK) rc = ensure_cnt(ctx, nblk);
       if (rc != BH_OK) return rc;
-      p.ws = (float *)ctx->ws;
-      p.cnt = (uint32_t *)ctx->cnt;
+      p.ws = ws_of(ctx);
+      p.cnt = cnt_of(ctx);
     }
     return bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, true, what);
   }
@@ -1014,8 +1008,8 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
     int rc = ensure_ws(ctx, (size_t)2 * G * c.BM * c.BN * 4);
     if (rc == BH_OK) rc = ensure_cnt(ctx, nblk);
     if (rc != BH_OK) return rc;
-    p.ws = (float *)ctx->ws;
-    p.cnt = (uint32_t *)ctx->cnt;
+    p.ws = ws_of(ctx);
+    p.cnt = cnt_of(ctx);
     void *args[] = {&p};
     return bh::launch(ctx, (const void *)k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, first, true, what);
   }
@@ -1033,11 +1027,11 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
   if (S > 1) {
     int rc = ensure_ws(ctx, (size_t)S * nblk * c.BM * c.BN * 4);
     if (rc != BH_OK) return rc;
-    p.ws = (float *)ctx->ws;
+    p.ws = ws_of(ctx);
     if (red == 2) {
       rc = ensure_cnt(ctx, nblk);
       if (rc != BH_OK) return rc;
-      p.cnt = (uint32_t *)ctx->cnt;
+      p.cnt = cnt_of(ctx);
       return bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, true, what);
     }
     rc = bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, false, what);

@@ -435,8 +435,18 @@ int launch_wino_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uin
 // floats of the k-major bank (the first part of every pack)
 size_t kmajor_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX);
 // split-K / stream-K workspace and arrival tickets of the context (bh_gemm.hip)
+// Inside a captured narrow op these are the scratch of the lane the op runs on (bh_common.h, capture
+// lanes): read the pointers through ws_of / cnt_of after the ensure_* call, never from the context.
 int ensure_ws(bh_ctx *ctx, size_t bytes);
 int ensure_cnt(bh_ctx *ctx, uint64_t n);
+inline float *ws_of(bh_ctx *ctx) {
+  const bh::op_scope *s = ctx->sched.scope;
+  return (float *)(s && s->lane > 0 ? ctx->sched.lane[s->lane].ws : ctx->ws);
+}
+inline uint32_t *cnt_of(bh_ctx *ctx) {
+  const bh::op_scope *s = ctx->sched.scope;
+  return (uint32_t *)(s && s->lane > 0 ? ctx->sched.lane[s->lane].cnt : ctx->cnt);
+}
 int launch_xpose_filts(bh_ctx *ctx, const float *w, float *wp, uint32_t OC, uint32_t IC, uint32_t KYX, bool first,
                        bool last);
 int ensure_wpack(bh_ctx *ctx, size_t bytes);

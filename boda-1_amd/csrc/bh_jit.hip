@@ -120,6 +120,7 @@ int bh_jit_launch(bh_ctx *c, int module_id, const char *name, void **args, uint3
   auto fit = it->second.funcs.find(name);
   if (fit == it->second.funcs.end())
     return bh::fail(BH_ERR, std::string("jit launch: '") + name + "' is not a function of the module");
+  if (int rc = bh::barrier(c)) return rc;  // behind every capture lane
   // global size in work-items (hipExtModuleLaunchKernel takes the grid in threads)
   BH_HIP(hipExtModuleLaunchKernel(fit->second, blks * tpb, 1, 1, tpb, 1, 1, 0, c->stream, args, nullptr, c->t_start,
                                   c->t_stop, 0));

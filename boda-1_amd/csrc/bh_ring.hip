@@ -999,7 +999,7 @@ int launch_pack_banks(bh_ctx *ctx, const float *filts, float *packed, uint32_t O
 }
 
 int ensure_wpack(bh_ctx *ctx, size_t bytes) {
-  return bh::grow_buffer(ctx, ctx->wpack, ctx->wpack_bytes, bytes, false, "filter-bank pack buffer");
+  return bh::lane_wpack(ctx, bytes);
 }
 
 }  // namespace bhk

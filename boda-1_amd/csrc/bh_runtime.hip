@@ -65,17 +65,204 @@ int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, c
   return BH_OK;
 }
 
+// ---- capture lanes (DESIGN.md "Capture lanes") ----
+// MI355X peaks, as boda_hip/runner.py's roofline_secs: fp32 matrix 157.3 TFLOP/s, HBM3E 8.0 TB/s
+constexpr double PEAK_FP32_FLOPS = 157.3e12, PEAK_HBM_BPS = 8.0e12;
+constexpr int DEFAULT_LANES = 4;
+constexpr double DEFAULT_NARROW_US = 200.0;  // every conv of the benchmark sets; DESIGN.md has the sweep
+constexpr double DEFAULT_FORK_US = 20.0;     // roofline time on every open lane before another is opened
+
+op_scope::op_scope(bh_ctx *ctx, double flops, double bytes) : c(ctx) {
+  est_us = std::max(flops / PEAK_FP32_FLOPS, bytes / PEAK_HBM_BPS) * 1e6;
+  narrow = est_us < ctx->sched.narrow_us;
+  ctx->sched.scope = this;
+}
+
+namespace {
+// the stream of lane k of the running capture
+hipStream_t lane_stream(bh_ctx *ctx, int k) { return k > 0 ? ctx->sched.lane[k].stream : ctx->stream; }
+
+int next_event(bh_ctx *ctx, hipEvent_t &ev) {
+  bh_sched &sc = ctx->sched;
+  if (sc.ev_used == sc.ev.size()) {
+    hipEvent_t e;
+    BH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    sc.ev.push_back(e);
+  }
+  ev = sc.ev[sc.ev_used++];
+  return BH_OK;
+}
+
+// stream `to` runs behind everything issued to stream `from` so far
+int order_after(bh_ctx *ctx, hipStream_t from, hipStream_t to) {
+  hipEvent_t ev;
+  if (int rc = next_event(ctx, ev)) return rc;
+  BH_HIP(hipEventRecord(ev, from));
+  BH_HIP(hipStreamWaitEvent(to, ev, 0));
+  return BH_OK;
+}
+
+// Join every side lane that holds un-joined work into the context's stream. The lanes' flags are
+// cleared first: after a failure the scheduler stays consistent (the capture itself is then invalid
+// and ends in bh_capture_end's error).
+int join_streams(bh_ctx *ctx) {
+  bh_sched &sc = ctx->sched;
+  int rc = BH_OK;
+  bool any = false;
+  for (int k = 1; k < sc.lanes; ++k) {
+    if (!sc.lane[k].forked) continue;
+    sc.lane[k].forked = false;
+    any = true;
+    if (rc == BH_OK) rc = order_after(ctx, sc.lane[k].stream, ctx->stream);
+  }
+  if (any) ++sc.cur[2];
+  return rc;
+}
+
+int grow_lane(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero) {
+  if (have >= want) return BH_OK;
+  if (buf) {  // as grow_buffer: a captured graph may still replay this pointer
+    bool live_graph = false;
+    for (hipGraphExec_t g : ctx->graphs) live_graph |= g != nullptr;
+    if (live_graph) {
+      ctx->retired.push_back(buf);
+    } else {
+      BH_HIP(hipStreamSynchronize(ctx->stream));
+      BH_HIP(hipFree(buf));
+    }
+  }
+  buf = nullptr;
+  have = 0;
+  BH_HIP(hipMalloc(&buf, want));
+  if (zero) BH_HIP(hipMemsetAsync(buf, 0, want, ctx->stream));
+  have = want;
+  return BH_OK;
+}
+}  // namespace
+
+int barrier(bh_ctx *ctx) {
+  bh_sched &sc = ctx->sched;
+  if (!sc.capturing || sc.lanes <= 1) return BH_OK;
+  sc.trk.join();
+  return join_streams(ctx);
+}
+
+int lane_resolve(bh_ctx *ctx, size_t ws_need) {
+  bh_sched &sc = ctx->sched;
+  op_scope *s = sc.scope;
+  if (!sc.capturing || !s || s->resolved) return BH_OK;
+  s->resolved = true;
+  ++sc.cur[3];
+  bh_lanes::placement p;
+  if (sc.lanes > 1) {
+    if (!s->narrow) {  // a wide op has the device to itself, on the context's stream
+      if (int rc = barrier(ctx)) return rc;
+    } else {
+      // scratch never grows inside a capture: an op that needs more than a side lane holds takes
+      // lane 0 and the context's own scratch
+      p = sc.trk.place(s->acc, s->est_us, (s->pin0 || ws_need > sc.lane[1].ws_bytes) ? 0 : -1);
+      if (p.join_first)
+        if (int rc = join_streams(ctx)) return rc;
+    }
+  }
+  sc.used_mask |= 1u << p.lane;
+  sc.cur_trace.push_back((uint32_t)p.lane | p.wait_mask << 8);
+  hipStream_t mine = lane_stream(ctx, p.lane);
+  if (p.lane > 0 && !sc.lane[p.lane].forked) {  // the lane's first use since the last join: fork
+    sc.lane[p.lane].forked = true;
+    if (int rc = order_after(ctx, ctx->stream, mine)) return rc;
+  }
+  for (int j = 0; j < sc.lanes; ++j)
+    if (p.wait_mask >> j & 1) {
+      ++sc.cur[1];
+      if (int rc = order_after(ctx, lane_stream(ctx, j), mine)) return rc;
+    }
+  s->lane = p.lane;  // from here on the call's launches and scratch are this lane's
+  return BH_OK;
+}
+
+int lane_ws(bh_ctx *ctx, size_t bytes) {
+  bh_sched &sc = ctx->sched;
+  if (int rc = lane_resolve(ctx, bytes)) return rc;
+  if (sc.scope && sc.scope->lane > 0) {
+    if (bytes <= sc.lane[sc.scope->lane].ws_bytes) return BH_OK;
+    return fail(BH_ERR, "split-K workspace: the per-lane workspace must grow (" + std::to_string(bytes) +
+                            " bytes) while the stream is being captured; run this op once eagerly before capturing");
+  }
+  if (!sc.capturing && sc.scope && sc.scope->narrow) sc.hw_ws = std::max(sc.hw_ws, bytes);
+  return grow_buffer(ctx, ctx->ws, ctx->ws_bytes, bytes, false, "split-K workspace");
+}
+
+int lane_cnt(bh_ctx *ctx, uint64_t n) {
+  bh_sched &sc = ctx->sched;
+  if (int rc = lane_resolve(ctx, 0)) return rc;
+  if (sc.scope && sc.scope->lane > 0) {
+    // side lanes hold as many tickets as the context did when the capture began
+    if (n <= sc.lane[sc.scope->lane].cnt_n) return BH_OK;
+    return fail(BH_ERR, "split-K tickets: the per-lane tickets must grow (" + std::to_string(n) +
+                            ") while the stream is being captured; run this op once eagerly before capturing");
+  }
+  size_t have = ctx->cnt_n * 4;
+  int rc = grow_buffer(ctx, ctx->cnt, have, std::max<uint64_t>(n, 4096) * 4, true, "split-K tickets");
+  ctx->cnt_n = have / 4;
+  return rc;
+}
+
+int lane_wpack(bh_ctx *ctx, size_t bytes) {
+  bh_sched &sc = ctx->sched;
+  int rc = grow_buffer(ctx, ctx->wpack, ctx->wpack_bytes, bytes, false, "filter-bank pack buffer");
+  if (rc != BH_OK || !sc.capturing || !sc.scope) return rc;
+  // one pack buffer per context: the op writes then reads it, so it conflicts with every other
+  // outstanding op that repacks
+  if (sc.scope->resolved) return fail(BH_ERR, "filter-bank pack buffer requested after the call's lane was picked");
+  sc.scope->write(ctx->wpack, ctx->wpack_bytes);
+  sc.scope->pin0 = true;  // and its other scratch is the context's, as its pack buffer
+  return BH_OK;
+}
+
 int launch(bh_ctx *ctx, const void *kernel, dim3 grid, dim3 block, void **args, bool first, bool last,
            const char *what, uint32_t shmem) {
+  hipStream_t stream = ctx->stream;
+  if (ctx->sched.capturing) {
+    // a scoped call's kernels go to its lane; anything else runs behind all lanes
+    if (int rc = ctx->sched.scope ? lane_resolve(ctx, 0) : barrier(ctx)) return rc;
+    if (ctx->sched.scope) stream = lane_stream(ctx, ctx->sched.scope->lane);
+  }
   hipEvent_t b = first ? ctx->t_start : nullptr, e = last ? ctx->t_stop : nullptr;
-  hipError_t r = (b || e) ? hipExtLaunchKernel(kernel, grid, block, args, shmem, ctx->stream, b, e, 0)
-                          : hipLaunchKernel(kernel, grid, block, args, shmem, ctx->stream);
+  hipError_t r = (b || e) ? hipExtLaunchKernel(kernel, grid, block, args, shmem, stream, b, e, 0)
+                          : hipLaunchKernel(kernel, grid, block, args, shmem, stream);
   if (first) ctx->t_start = nullptr;
   if (last) ctx->t_stop = nullptr;
   if (r != hipSuccess) return fail(BH_ERR, std::string("launch of ") + what + " failed: " + hipGetErrorString(r));
   return check_launch(what);
 }
 }  // namespace bh
+
+namespace {
+// the bytes a forward conv call touches, for the capture lanes: `out` is the first byte the call
+// writes (its channel slab in image 0); a slab call covers through the end of its slab in the last image
+void conv_scope(bh::op_scope &s, const float *in, const float *filts, const float *packed, uint32_t banks,
+                const float *biases, const float *res, const float *out, uint32_t out_ctot, uint32_t B, uint32_t IC,
+                uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX, uint64_t ohw) {
+  s.read(in, (uint64_t)B * IC * H * W * 4);
+  s.read(filts, (uint64_t)OC * IC * KY * KX * 4);
+  if (packed) s.read(packed, (uint64_t)bh::conv_filts_packed_floats(OC, IC, KY, KX, banks) * 4);
+  s.read(biases, (uint64_t)OC * 4);
+  s.read(res, (uint64_t)B * OC * ohw * 4);
+  s.write(out, ((uint64_t)(B - 1) * (out_ctot ? out_ctot : OC) + OC) * ohw * 4);
+}
+uint64_t conv_ohw(uint32_t H, uint32_t W, uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py,
+                  uint32_t px) {
+  return (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
+}
+}  // namespace
+
+// roofline flops / bytes of a forward conv, as boda_hip/ops.py's ConvShape
+#define BH_CONV_SCOPE(packed_, banks_, res_, out_, ctot_)                                                        \
+  const uint64_t sc_ohw_ = conv_ohw(H, W, KY, KX, sy, sx, py, px);                                                \
+  bh::op_scope bh_op_scope_(c, 2.0 * B * sc_ohw_ * OC * IC * KY * KX,                                             \
+                            4.0 * ((double)B * IC * H * W + (double)B * OC * sc_ohw_ + (double)OC * IC * KY * KX)); \
+  conv_scope(bh_op_scope_, in, filts, packed_, banks_, biases, res_, out_, ctot_, B, IC, H, W, OC, KY, KX, sc_ohw_)
 
 extern "C" {
 
@@ -115,7 +302,28 @@ int bh_init(int device, bh_ctx **out) {
     e = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device);
     c->stamp_hz = khz > 0 ? khz * 1000.0 : 100e6;
   }
+  // capture lanes: BH_CAPTURE_LANES streams (1: one chain, as without the scheduler), ops with a
+  // roofline time under BH_CAPTURE_NARROW_US spread over them. Replaying a graph with parallel
+  // branches needs four hardware queues on this runtime: with fewer configured, one lane.
+  bh_sched &sc = c->sched;
+  sc.lanes = bh::DEFAULT_LANES;
+  sc.narrow_us = bh::DEFAULT_NARROW_US;
+  if (const char *v = getenv("BH_CAPTURE_LANES")) sc.lanes = atoi(v);
+  if (const char *v = getenv("BH_CAPTURE_NARROW_US")) sc.narrow_us = atof(v);
+  double fork_us = bh::DEFAULT_FORK_US;
+  if (const char *v = getenv("BH_CAPTURE_FORK_US")) fork_us = atof(v);
+  if (const char *v = getenv("GPU_MAX_HW_QUEUES"))
+    if (atoi(v) < 4) sc.lanes = 1;
+  sc.lanes = std::max(1, std::min(sc.lanes, (int)bh_lanes::MAX_LANES));
+  for (int k = 1; k < sc.lanes && e == hipSuccess; ++k)
+    e = hipStreamCreateWithFlags(&sc.lane[k].stream, hipStreamNonBlocking);
+  sc.trk.reset(sc.lanes);
+  sc.trk.set_fork_us(fork_us);
   if (e != hipSuccess) {
+    for (int k = 1; k < bh_lanes::MAX_LANES; ++k)
+      if (sc.lane[k].stream) (void)hipStreamDestroy(sc.lane[k].stream);
+    if (c->stamps) (void)hipFree(c->stamps);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return bh::fail(BH_ERR, std::string("bh_init: ") + hipGetErrorString(e));
   }
@@ -137,6 +345,14 @@ int bh_destroy(bh_ctx *c) {
   if (c->bckw) (void)hipFree(c->bckw);
   if (c->stamps) (void)hipFree(c->stamps);
   if (c->cnt) (void)hipFree(c->cnt);
+  for (int k = 1; k < bh_lanes::MAX_LANES; ++k) {
+    bh_lane &l = c->sched.lane[k];
+    if (l.stream) (void)hipStreamSynchronize(l.stream);
+    if (l.ws) (void)hipFree(l.ws);
+    if (l.cnt) (void)hipFree(l.cnt);
+    if (l.stream) (void)hipStreamDestroy(l.stream);
+  }
+  for (hipEvent_t ev : c->sched.ev) (void)hipEventDestroy(ev);
   (void)hipStreamDestroy(c->stream);
   delete c;
   return BH_OK;
@@ -155,6 +371,7 @@ int bh_plat_tag(bh_ctx *c, char *buf, size_t n) {
 int bh_get_stream(bh_ctx *c, void **s) {
   BH_ENTER(c);
   if (!s) return bh::fail(BH_ERR, "null out");
+  if (int rc = bh::barrier(c)) return rc;  // the caller's work runs behind every capture lane
   *s = (void *)c->stream;
   return BH_OK;
 }
@@ -184,6 +401,7 @@ int bh_free(bh_ctx *c, void *p) {
 
 int bh_memset0(bh_ctx *c, void *p, size_t bytes) {
   BH_ENTER(c);
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipMemsetAsync(p, 0, bytes, c->stream));
   return BH_OK;
 }
@@ -191,6 +409,7 @@ int bh_memset0(bh_ctx *c, void *p, size_t bytes) {
 int bh_h2d(bh_ctx *c, void *d, const void *h, size_t bytes) {
   BH_ENTER(c);
   // synchronous w.r.t. the host buffer (caller may free it on return)
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
   BH_HIP(hipStreamSynchronize(c->stream));
   return BH_OK;
@@ -198,6 +417,7 @@ int bh_h2d(bh_ctx *c, void *d, const void *h, size_t bytes) {
 
 int bh_d2h(bh_ctx *c, void *h, const void *d, size_t bytes) {
   BH_ENTER(c);
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
   BH_HIP(hipStreamSynchronize(c->stream));
   return BH_OK;
@@ -217,6 +437,7 @@ int bh_event_record(bh_ctx *c, int *id) {
     BH_HIP(hipEventCreate(&ev));
     c->events.push_back(ev);
   }
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipEventRecord(c->events[c->events_used], c->stream));
   *id = c->events_used++;
   return BH_OK;
@@ -263,6 +484,10 @@ int bh_sgemm_kmajor(bh_ctx *c, const float *a, const float *b, float *cc, uint32
   BH_ENTER_CALL(c);
   if (!a || !b || !cc) return bh::fail(BH_ERR, "null tensor");
   if (!M || !N || !K) return bh::fail(BH_UNSUP, "sgemm: zero-sized dimension");
+  bh::op_scope scope(c, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N));
+  scope.read(a, (uint64_t)K * M * 4);
+  scope.read(b, (uint64_t)K * N * 4);
+  scope.write(cc, (uint64_t)M * N * 4);
   return bh::launch_sgemm(c, a, b, cc, M, N, K);
 }
 
@@ -274,6 +499,7 @@ int bh_conv2d_fwd_nchw_pk(bh_ctx *c, const float *in, const float *filts, const 
   if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
     return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
   if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
+  BH_CONV_SCOPE(packed, BH_BANKS_ALL, nullptr, out, 0);
   return bh::launch_conv(c, in, filts, packed, biases, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu);
 }
 
@@ -285,6 +511,7 @@ int bh_conv2d_fwd_nchw_res(bh_ctx *c, const float *in, const float *filts, const
   if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
     return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
   if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
+  BH_CONV_SCOPE(packed, BH_BANKS_ALL, res, out, 0);
   return bh::launch_conv(c, in, filts, packed, biases, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0, res);
 }
 
@@ -299,6 +526,7 @@ int bh_conv2d_fwd_nchw_slab(bh_ctx *c, const float *in, const float *filts, cons
   if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
   if ((uint64_t)out_chan_ofs + OC > out_chans_total) return bh::fail(BH_ERR, "conv: output channel slab out of range");
   const uint64_t ohw = (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
+  BH_CONV_SCOPE(packed, BH_BANKS_ALL, nullptr, out + out_chan_ofs * ohw, out_chans_total);
   return bh::launch_conv(c, in, filts, packed, biases, out + out_chan_ofs * ohw, B, IC, H, W, OC, KY, KX, sy, sx,
                          py, px, relu, out_chans_total);
 }
@@ -316,6 +544,7 @@ int bh_conv2d_fwd_nchw_pkb(bh_ctx *c, const float *in, const float *filts, const
   if ((uint64_t)out_chan_ofs + OC > out_chans_total) return bh::fail(BH_ERR, "conv: output channel slab out of range");
   if (res && out_chans_total != OC) return bh::fail(BH_ERR, "conv: residual and channel slab together");
   const uint64_t ohw = (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
+  BH_CONV_SCOPE(packed, banks, res, out + out_chan_ofs * ohw, out_chans_total);
   return bh::launch_conv(c, in, filts, packed, biases, out + out_chan_ofs * ohw, B, IC, H, W, OC, KY, KX, sy, sx, py,
                          px, relu, out_chans_total, res, false, false, banks);
 }
@@ -509,6 +738,7 @@ int bh_stamp(bh_ctx *c, int slot) {
   if (slot < 0 || slot >= STAMP_SLOTS) return bh::fail(BH_ERR, "stamp slot out of range");
   unsigned long long *t = (unsigned long long *)c->stamps;
   void *args[] = {&t, &slot};
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipLaunchKernel((const void *)stamp_kernel, dim3(1), dim3(64), args, 0, c->stream));
   return bh::check_launch("stamp");
 }
@@ -518,6 +748,7 @@ int bh_spin(bh_ctx *c, int us) {
   if (us < 1 || us > 100000) return bh::fail(BH_ERR, "bh_spin: us out of range 1..100000");
   unsigned long long ticks = (unsigned long long)us * (unsigned long long)(c->stamp_hz / 1e6);
   void *args[] = {&ticks};
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipLaunchKernel((const void *)spin_kernel, dim3(1), dim3(64), args, 0, c->stream));
   return bh::check_launch("spin");
 }
@@ -526,6 +757,7 @@ int bh_stamps_read(bh_ctx *c, int first, int n, double *us) {
   BH_ENTER(c);
   if (!us || first < 0 || n < 0 || first + n > STAMP_SLOTS) return bh::fail(BH_ERR, "bad stamp range");
   std::vector<unsigned long long> t(n);
+  if (int rc = bh::barrier(c)) return rc;
   BH_HIP(hipMemcpyAsync(t.data(), (unsigned long long *)c->stamps + first, n * sizeof(unsigned long long),
                         hipMemcpyDeviceToHost, c->stream));
   BH_HIP(hipStreamSynchronize(c->stream));
@@ -535,7 +767,26 @@ int bh_stamps_read(bh_ctx *c, int first, int n, double *us) {
 
 int bh_capture_begin(bh_ctx *c) {
   BH_ENTER(c);
+  bh_sched &sc = c->sched;
+  if (sc.capturing) return bh::fail(BH_ERR, "bh_capture_begin: the context is already capturing");
+  // side-lane scratch never grows inside a capture: bring it up to what eager narrow ops asked for
+  // (workspace) and to the context's own tickets (zero-filled, as the context's) now
+  for (int k = 1; k < sc.lanes; ++k) {
+    bh_lane &l = sc.lane[k];
+    if (int rc = bh::grow_lane(c, l.ws, l.ws_bytes, sc.hw_ws, false)) return rc;
+    size_t have = l.cnt_n * 4;
+    int rc = bh::grow_lane(c, l.cnt, have, c->cnt_n * 4, true);
+    l.cnt_n = have / 4;
+    if (rc != BH_OK) return rc;
+    l.forked = false;
+  }
   BH_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  sc.capturing = true;
+  sc.trk.join();
+  sc.ev_used = 0;
+  sc.used_mask = 0;
+  sc.cur_trace.clear();
+  for (uint32_t &v : sc.cur) v = 0;
   return BH_OK;
 }
 
@@ -543,13 +794,43 @@ int bh_capture_end(bh_ctx *c, int *graph_id) {
   BH_ENTER(c);
   if (!graph_id) return bh::fail(BH_ERR, "null out");
   hipGraph_t g = nullptr;
+  bh_sched &sc = c->sched;
+  // whatever happened inside the capture, the scheduler leaves it here: all lanes joined, nothing
+  // outstanding (a join that fails means the capture is invalid; hipStreamEndCapture reports that)
+  const int jrc = bh::barrier(c);
+  const std::string jmsg = jrc == BH_OK ? std::string() : std::string(bh_last_error());
+  sc.capturing = false;
+  sc.trk.join();
+  for (int k = 1; k < sc.lanes; ++k) sc.lane[k].forked = false;
   BH_HIP(hipStreamEndCapture(c->stream, &g));
+  if (jrc != BH_OK) {
+    if (g) (void)hipGraphDestroy(g);
+    return bh::fail(BH_ERR, "bh_capture_end: joining the capture lanes failed: " + jmsg);
+  }
+  sc.stats[0] = (uint32_t)__builtin_popcount(sc.used_mask);
+  for (int i = 1; i < 4; ++i) sc.stats[i] = sc.cur[i];
+  sc.trace = sc.cur_trace;
   hipGraphExec_t ge = nullptr;
   hipError_t e = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
   (void)hipGraphDestroy(g);
   if (e != hipSuccess) return bh::fail(BH_ERR, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
   c->graphs.push_back(ge);
   *graph_id = (int)c->graphs.size() - 1;
+  return BH_OK;
+}
+
+int bh_capture_stats(bh_ctx *c, uint32_t out[4]) {
+  BH_CHECK_CTX(c);
+  if (!out) return bh::fail(BH_ERR, "null out");
+  for (int i = 0; i < 4; ++i) out[i] = c->sched.stats[i];
+  return BH_OK;
+}
+
+int bh_capture_trace(bh_ctx *c, uint32_t *out, uint32_t cap, uint32_t *n) {
+  BH_CHECK_CTX(c);
+  if (!n || (cap && !out)) return bh::fail(BH_ERR, "null out");
+  *n = (uint32_t)c->sched.trace.size();
+  for (uint32_t i = 0; i < cap && i < *n; ++i) out[i] = c->sched.trace[i];
   return BH_OK;
 }
 

@@ -1056,8 +1056,8 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
       int rc = ensure_ws(ctx, (size_t)2 * G * slab * 4);
       if (rc == BH_OK) rc = ensure_cnt(ctx, units);
       if (rc != BH_OK) return rc;
-      p.ws = (float *)ctx->ws;
-      p.cnt = (uint32_t *)ctx->cnt;
+      p.ws = ws_of(ctx);
+      p.cnt = cnt_of(ctx);
     }
   } else if (c.dc_wpm) {
     // stream-K: as many blocks as are resident at once, the (unit, stage) iterations dealt equally
@@ -1075,8 +1075,8 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
     int rc = ensure_ws(ctx, (size_t)2 * G * slab * 4);
     if (rc == BH_OK) rc = ensure_cnt(ctx, units);
     if (rc != BH_OK) return rc;
-    p.ws = (float *)ctx->ws;
-    p.cnt = (uint32_t *)ctx->cnt;
+    p.ws = ws_of(ctx);
+    p.cnt = cnt_of(ctx);
   }
 #ifdef BH_KTRACE
   p.trace = (unsigned long long *)ctx->stamps + 65536;

@@ -1083,8 +1083,8 @@ int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, cons
   int rc = ensure_ws(ctx, (size_t)2 * G * NT * 16 * 16);  // two slabs of 16 float4 per thread per block
   if (rc == BH_OK) rc = ensure_cnt(ctx, (size_t)ntile);
   if (rc != BH_OK) return rc;
-  p.ws = (float *)ctx->ws;
-  p.cnt = (uint32_t *)ctx->cnt;
+  p.ws = ws_of(ctx);
+  p.cnt = cnt_of(ctx);
 #ifdef BH_KTRACE
   p.trace = (unsigned long long *)ctx->stamps + 65536;
 #endif

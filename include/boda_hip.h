@@ -96,6 +96,21 @@ int bh_capture_begin(bh_ctx *ctx);
 int bh_capture_end(bh_ctx *ctx, int *graph_id);
 int bh_graph_launch(bh_ctx *ctx, int graph_id);
 int bh_graph_destroy(bh_ctx *ctx, int graph_id);
+/* Added within ABI 3 (callers of the functions above need no change): capture lanes. While the
+ * context captures, independent narrow ops (bh_sgemm_kmajor and the bh_conv2d_fwd_nchw* calls whose
+ * roofline time is below BH_CAPTURE_NARROW_US microseconds) are spread over up to BH_CAPTURE_LANES
+ * streams (environment, read by bh_init; 1 = one chain of dependent launches; at most 4; one lane
+ * when GPU_MAX_HW_QUEUES is set below 4), so the graph gets parallel branches. A further stream is
+ * opened only once every open one holds BH_CAPTURE_FORK_US microseconds of estimated work since the
+ * last join (short runs of ops between other calls stay one chain). Ops whose byte ranges
+ * conflict (RAW, WAR, WAW) keep their order; every other call on the context joins all lanes first;
+ * eager calls are untouched and results are bit-identical.
+ * bh_capture_stats: of the most recent finished capture, out = {lanes used, cross-lane
+ * dependency edges, joins of all lanes, ops scheduled}.
+ * bh_capture_trace: per scheduled op of that capture, in call order, lane | wait_mask << 8
+ * (wait_mask: the other lanes whose tail the op waited for); writes min(cap, *n) entries. */
+int bh_capture_stats(bh_ctx *ctx, uint32_t out[4]);
+int bh_capture_trace(bh_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n);
 
 /* ---- deterministic test data on the device: the gen_data_* kernels
  *      (test/rtc/gen-util.h:1-9, gen_data_sgemm_{a,b}.cucl,
