@@ -351,8 +351,10 @@ int launch_in(bh_ctx *ctx, BckArgs &p, const bck_dims &s, const float *packed) {
       if (rc != BH_OK) return rc;
       wt = (const float *)ctx->bckw;
     }
-    return bh::launch_conv(ctx, p.ogl, wt, fpk, nullptr, p.in_grad, p.B, p.OC, p.OH, p.OW, p.IC, p.KY, p.KX, 1, 1,
-                           p.KY - 1 - p.py, p.KX - 1 - p.px, 0);
+    bh::conv_call cc{p.ogl, wt, fpk, BANKS_ALL, nullptr, nullptr, p.in_grad, p.B, p.OC, p.OH, p.OW, p.IC, p.KY, p.KX,
+                     1, 1, p.KY - 1 - p.py, p.KX - 1 - p.px, 0, 0};
+    cc.finish();
+    return bh::launch_conv(ctx, cc);
   }
   const int cfg = bcki_cfg(ctx, s);
   const uint32_t bn = cfg ? 256 : 128;

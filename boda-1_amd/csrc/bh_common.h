@@ -129,6 +129,38 @@ inline fastdiv make_fastdiv(uint32_t d) {
   f.m = (uint32_t)(((1ull << 32) * ((1ull << s) - d)) / d + 1);
   return f;
 }
+// the magic number and shift of d into a kernel-argument pair (d == 0 is taken as 1)
+inline void set_fd(uint32_t d, uint32_t &m, uint32_t &s) {
+  const fastdiv f = make_fastdiv(d ? d : 1);
+  m = f.m;
+  s = f.s;
+}
+
+inline uint32_t num_cus(const bh_ctx *ctx) {
+  return ctx->prop.multiProcessorCount > 0 ? (uint32_t)ctx->prop.multiProcessorCount : 256u;
+}
+// per-block device-clock marks of the instrumented library (tools/ktrace.py); nothing otherwise
+template <class Args>
+inline void set_trace(bh_ctx *ctx, Args &p) {
+#ifdef BH_KTRACE
+  p.trace = (unsigned long long *)ctx->stamps + 65536;
+#else
+  (void)ctx;
+  (void)p;
+#endif
+}
+// blocks of nt threads with lds bytes of dynamic LDS a CU holds at once (1 when the query fails)
+inline int occupancy(const void *k, int nt, size_t lds = 0) {
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, nt, lds) != hipSuccess || occ < 1) occ = 1;
+  return occ;
+}
+// let kernel k take lds bytes of dynamic LDS (what: the BH_ERR message when the runtime refuses)
+inline int dyn_lds(const void *k, uint32_t lds, const char *what) {
+  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return fail(BH_ERR, what);
+  return BH_OK;
+}
 
 }  // namespace bh
 
@@ -186,11 +218,27 @@ namespace bh {
 int launch_gen_data(bh_ctx *ctx, int kind, float *dst, const uint32_t dims[4], uint32_t mode, float vi);
 int launch_sgemm(bh_ctx *ctx, const float *a, const float *b, float *c, uint32_t M, uint32_t N, uint32_t K);
 int tune_set_wt(bh_ctx *ctx, int op, int wt);
-int launch_conv(bh_ctx *ctx, const float *in, const float *filts, const float *packed, const float *biases,
-                float *out, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
-                uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu, uint32_t out_ctot = 0,
-                const float *res = nullptr, bool no_dc = false, bool repacked = false,
-                uint32_t pk_banks = 0xffffffffu);
+// One forward conv call: out = act(conv(in, filts) + biases [+ res]).
+struct conv_call {
+  const float *in, *filts;
+  const float *packed;  // the caller's pack of filts (may be null: a route that reads a pack makes its own)
+  uint32_t pk_banks;    // the Winograd banks (BH_BANK_*) packed holds behind its k-major bank
+  const float *biases, *res;  // may be null; res is laid out like an OC-channel out
+  float *out;                 // the first byte written: the call's channel slab in image 0
+  uint32_t B, IC, H, W, OC, KY, KX, sy, sx, py, px;
+  int relu;
+  // channels of the tensor `out` points into (0: OC). Every conv epilogue addresses image i of the
+  // output at i * out_ctot * OH * OW, so a conv can write its channel slab of a wider tensor (a
+  // Concat's output) in place.
+  uint32_t out_ctot;
+  uint32_t OH = 0, OW = 0;  // derived by finish()
+  void finish() {
+    if (!out_ctot) out_ctot = OC;
+    OH = (H + 2 * py - KY) / sy + 1;
+    OW = (W + 2 * px - KX) / sx + 1;
+  }
+};
+int launch_conv(bh_ctx *ctx, const conv_call &cc);  // cc finished
 // packs (bhk::launch_pack_banks): the k-major bank + the Winograd banks of `banks` (BH_BANK_*)
 size_t conv_filts_packed_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX, uint32_t banks);
 int launch_conv_filts_pack(bh_ctx *ctx, const float *filts, float *packed, uint32_t OC, uint32_t IC, uint32_t KY,

@@ -30,6 +30,7 @@
 #include "bh_gemm_dev.h"
 
 namespace bhk {
+static int launch_dcm(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 namespace {
 
 // logical block of hardware block bid: blocks b, b+8, ... share an XCD under round-robin
@@ -410,13 +411,14 @@ template <int KY, int KX, int WPM, int RIN, int V4, int CI, int TM, int TN, int 
 cfg_t dcm_cfg(const char *name) {
   cfg_t c{name, 32 * TM * WO, 128 * TN, CI * KY * KX, 256 * WO, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = dcm_kernel<KY, KX, WPM, RIN, V4, CI, TM, TN, WO, D, DBG>;
-  c.dc = 2;
-  c.dc_ky = KY;
-  c.dc_kx = KX;
-  c.dc_s = V4;  // dcm: 16-B strip pieces (rows of W % 4 == 0)
-  c.dc_wpm = WPM;
-  c.dc_rin = RIN;
-  c.dc_ci = CI;
+  c.family = F_DCM;
+  c.launch = launch_dcm;
+  c.ky = KY;
+  c.kx = KX;
+  c.v4 = V4;
+  c.wpm = WPM;
+  c.strip_rows = RIN;
+  c.kc = CI;
   return c;
 }
 
@@ -482,18 +484,18 @@ std::vector<cfg_t> dcm_cfgs() {
 // of its channel group and every tile's strip fitting. splits: 0 / 1..4 = blocks per CU with
 // the (tile, channel group) iterations dealt equally; 5..8 = blocks per CU 1..4, whole tiles
 // per block.
-int launch_dcm(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-               uint32_t sx, uint32_t splits, bool first) {
-  if ((int)KY != c.dc_ky || (int)KX != c.dc_kx || sy != 1 || sx != 1 || p.py >= KY)
+static int launch_dcm(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r) {
+  const uint32_t KY = cc.KY, KX = cc.KX, splits = r.splits;
+  if ((int)KY != c.ky || (int)KX != c.kx || cc.sy != 1 || cc.sx != 1 || p.py >= KY)
     return bh::fail(BH_UNSUP, std::string("conv: direct config ") + c.name + " is for another kernel / stride");
-  if (p.IC % (uint32_t)c.dc_ci)
+  if (p.IC % (uint32_t)c.kc)
     return bh::fail(BH_UNSUP, std::string("conv: input channels not a multiple of ") + c.name + "'s group");
   const uint32_t npx = (uint32_t)c.BN, OW = p.OW, OHW = p.OHW, Hp = p.H + 2 * p.py;
   const bool p1 = KY == 1 && KX == 1;
   if (p1) {  // 1x1: strip = the tile's pixels; 16-B pieces need quads inside one image
-    if (p.py || p.px || (c.dc_s && OHW % 4))
+    if (p.py || p.px || (c.v4 && OHW % 4))
       return bh::fail(BH_UNSUP, std::string("conv: padded 1x1 / pixel quads across images for ") + c.name);
-  } else if (p.W + p.px > (uint32_t)c.dc_wpm || p.px > 4 || (c.dc_s && p.W % 4)) {
+  } else if (p.W + p.px > (uint32_t)c.wpm || p.px > 4 || (c.v4 && p.W % 4)) {
     // strip pitch: the row plus a zero tail wide enough for the horizontal padding
     return bh::fail(BH_UNSUP, std::string("conv: input rows do not fit the strip of ") + c.name);
   }
@@ -505,23 +507,21 @@ int launch_dcm(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY
     const uint32_t va = (a / OHW) * Hp + (a % OHW) / OW, vb = (b / OHW) * Hp + (b % OHW) / OW;
     rin = std::max(rin, vb - va + KY);
   }
-  if (!p1 && rin > (uint32_t)c.dc_rin)
+  if (!p1 && rin > (uint32_t)c.strip_rows)
     return bh::fail(BH_UNSUP, std::string("conv: pixel tile's input strip too large for ") + c.name);
-  const uint64_t out_bytes = (uint64_t)B * p.OCOHW * 4;
+  const uint64_t out_bytes = (uint64_t)cc.B * p.OCOHW * 4;
   if (out_bytes >= 0x7fffff00ull) return bh::fail(BH_UNSUP, "conv: output too large for the direct kernel");
   p.c_bytes = (uint32_t)out_bytes;
   const uint32_t octiles = (p.M + c.BM - 1) / c.BM;
-  const uint32_t ipt = p.IC / (uint32_t)c.dc_ci;
+  const uint32_t ipt = p.IC / (uint32_t)c.kc;
   const uint64_t ntile = (uint64_t)ptiles * octiles, total = ntile * ipt;
   if (total >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: too many iterations");
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, c.NT, 0) != hipSuccess || occ < 1) occ = 1;
+  const int occ = bh::occupancy(k, c.NT);
   const bool whole = splits > 4;
   uint32_t bpc = splits ? (whole ? splits - 4 : splits) : 2;
   bpc = std::max(1u, std::min<uint32_t>(bpc, (uint32_t)std::min(occ, 4)));
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  uint64_t G = (uint64_t)ncu * bpc;
+  uint64_t G = (uint64_t)bh::num_cus(ctx) * bpc;
   uint32_t ipb = (uint32_t)((total + G - 1) / G);
   if (whole) ipb = (uint32_t)((ntile + G - 1) / G) * ipt;
   G = (total + ipb - 1) / ipb;
@@ -529,26 +529,18 @@ int launch_dcm(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY
   p.ipb = ipb;
   p.total_it = (uint32_t)total;
   p.tiles_m = octiles;
-  p.tiles_n = B;  // images (strip rows past the last image miss)
-  bh::fastdiv f = bh::make_fastdiv(ipt);
-  p.ipt_m = f.m;
-  p.ipt_s = f.s;
-  f = bh::make_fastdiv(octiles);
-  p.tm_m = f.m;
-  p.tm_s = f.s;
-  f = bh::make_fastdiv(Hp);
-  p.kyx_m = f.m;
-  p.kyx_s = f.s;
+  p.tiles_n = cc.B;  // images (strip rows past the last image miss)
+  bh::set_fd(ipt, p.ipt_m, p.ipt_s);
+  bh::set_fd(octiles, p.tm_m, p.tm_s);
+  bh::set_fd(Hp, p.kyx_m, p.kyx_s);
   int rc = ensure_ws(ctx, (size_t)2 * G * c.BM * c.BN * 4);  // two tile slabs per block
   if (rc == BH_OK) rc = ensure_cnt(ctx, (size_t)ntile);
   if (rc != BH_OK) return rc;
   p.ws = ws_of(ctx);
   p.cnt = cnt_of(ctx);
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
-  return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, first, true, "conv_direct_mc");
+  return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, r.first, true, "conv_direct_mc");
 }
 
 }  // namespace bhk

@@ -26,6 +26,7 @@
 #include "bh_gemm_dev.h"
 
 namespace bhk {
+static int launch_dc(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 namespace {
 
 template <int KX, int WPM>
@@ -749,19 +750,25 @@ __global__ __launch_bounds__(NW * 64) void dcr_kernel(GemmArgs p) {
 #endif
 }
 
+// kernel KY x KX at stride S, strip of RIN rows at pitch WPM, V4: 16-B strip pieces (input rows of W % 4 == 0)
+void set_dc(cfg_t &c, int KY, int KX, int S, int WPM, int RIN, int V4) {
+  c.family = F_DIRECT;
+  c.launch = launch_dc;
+  c.ky = KY;
+  c.kx = KX;
+  c.stride = S;
+  c.wpm = WPM;
+  c.strip_rows = RIN;
+  c.v4 = V4;
+}
+
 template <int KY, int KX, int S, int WPM, int RIN, int TM, int NW, int D, int V4, int ICMAX, int DBG = 0, int PFO = 0,
           int PSL = 0>
 cfg_t dcr_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * NW, 2 * ((KY * KX + 1) / 2), 64 * NW, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = dcr_kernel<KY, KX, S, WPM, RIN, TM, NW, D, V4, ICMAX, DBG, PFO, PSL>;
-  c.dc_ci = V4;
-  c.dc = 1;
-  c.dc_ky = KY;
-  c.dc_kx = KX;
-  c.dc_s = S;
-  c.dc_wpm = WPM;
-  c.dc_rin = RIN;
-  c.dc_icmax = ICMAX;  // resident weights: input channels <= ICMAX, grid a multiple of the OC tiles
+  set_dc(c, KY, KX, S, WPM, RIN, V4);
+  c.icmax = ICMAX;  // resident weights: input channels <= ICMAX, grid a multiple of the OC tiles
   return c;
 }
 
@@ -769,13 +776,7 @@ template <int KY, int KX, int S, int WPM, int RIN, int TM, int TN, int D, int V4
 cfg_t dc_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 128 * TN, 2 * ((KY * KX + 1) / 2), 256, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = dc_kernel<KY, KX, S, WPM, RIN, TM, TN, D, V4, PSL, PFO>;
-  c.dc_ci = V4;  // dc == 1: 16-B strip pieces (input rows of W % 4 == 0)
-  c.dc = 1;
-  c.dc_ky = KY;
-  c.dc_kx = KX;
-  c.dc_s = S;
-  c.dc_wpm = WPM;
-  c.dc_rin = RIN;
+  set_dc(c, KY, KX, S, WPM, RIN, V4);
   return c;
 }
 
@@ -852,60 +853,50 @@ std::vector<cfg_t> dc_cfgs() {
 
 // Launch a direct-conv configuration (p filled by launch_conv with a = packed bank): UNSUP if
 // the shape is not this instantiation's (kernel, stride) or its strip would not fit.
-int launch_dc(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-              uint32_t sx, bool first) {
-  if ((int)KY != c.dc_ky || (int)KX != c.dc_kx || (int)sy != c.dc_s || (int)sx != c.dc_s)
+static int launch_dc(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r) {
+  const uint32_t KY = cc.KY, KX = cc.KX, sy = cc.sy, sx = cc.sx;
+  if ((int)KY != c.ky || (int)KX != c.kx || (int)sy != c.stride || (int)sx != c.stride)
     return bh::fail(BH_UNSUP, std::string("conv: direct config ") + c.name + " is for another kernel / stride");
   // strip columns: input x at column x + pxa; the rightmost tap column must exist (zero past W)
-  const bool v4 = c.dc_ci != 0;
+  const bool v4 = c.v4 != 0;
   if (v4 && (p.W % 4 || p.px > 4))
     return bh::fail(BH_UNSUP, std::string("conv: 16-B strip pieces need W % 4 == 0, pad <= 4 for ") + c.name);
   const uint32_t pxa = v4 ? (p.px ? 4u : 0u) : p.px;
   const uint64_t maxcol = (uint64_t)pxa + (uint64_t)(p.OW - 1) * sx + KX - 1 - p.px;
-  if (pxa + p.W > (uint32_t)c.dc_wpm || maxcol >= (uint64_t)c.dc_wpm)
+  if (pxa + p.W > (uint32_t)c.wpm || maxcol >= (uint64_t)c.wpm)
     return bh::fail(BH_UNSUP, std::string("conv: input row too wide for ") + c.name);
   const uint32_t npx = (uint32_t)c.BN, OW = p.OW, OHW = p.OHW;
   const uint32_t tiles = (OHW + npx - 1) / npx;
   // input rows the worst pixel tile touches
   for (uint32_t t = 0; t < tiles; ++t) {
     const uint32_t a = t * npx, b = std::min(OHW, a + npx) - 1;
-    if ((b / OW - a / OW) * sy + KY > (uint32_t)c.dc_rin)
+    if ((b / OW - a / OW) * sy + KY > (uint32_t)c.strip_rows)
       return bh::fail(BH_UNSUP, std::string("conv: pixel tile spans too many input rows for ") + c.name);
   }
-  const uint64_t out_bytes = (uint64_t)B * p.OCOHW * 4;
+  const uint64_t out_bytes = (uint64_t)cc.B * p.OCOHW * 4;
   if (out_bytes >= 0x7fffff00ull) return bh::fail(BH_UNSUP, "conv: output too large for the direct kernel");
   p.c_bytes = (uint32_t)out_bytes;
   const uint32_t octiles = (p.M + c.BM - 1) / c.BM;
-  const uint64_t ntile = (uint64_t)B * tiles * octiles;
+  const uint64_t ntile = (uint64_t)cc.B * tiles * octiles;
   if (ntile >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: too many tiles");
-  if (c.dc_icmax && p.IC > (uint32_t)c.dc_icmax)
-    return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " keeps at most " + std::to_string(c.dc_icmax) +
+  if (c.icmax && p.IC > (uint32_t)c.icmax)
+    return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " keeps at most " + std::to_string(c.icmax) +
                                   " input channels' weights resident");
   // persistent grid: as many blocks as fit on the device at once (each loops over tiles); the
   // resident-weight form: a multiple of the OC tiles, so that every block keeps one OC tile
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  int bpc = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, k, c.NT, 0) != hipSuccess || bpc < 1) bpc = 1;
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  uint32_t G = (uint32_t)std::min<uint64_t>(ntile, (uint64_t)ncu * std::min(bpc, 4));
-  if (c.dc_icmax) G = std::max(octiles, G / octiles * octiles);
+  const int bpc = bh::occupancy(k, c.NT);
+  uint32_t G = (uint32_t)std::min<uint64_t>(ntile, (uint64_t)bh::num_cus(ctx) * std::min(bpc, 4));
+  if (c.icmax) G = std::max(octiles, G / octiles * octiles);
   p.total_it = (uint32_t)ntile;
   p.tiles_n = tiles;
   p.ipt = octiles;
-  bh::fastdiv f = bh::make_fastdiv(tiles);
-  p.tm_m = f.m;
-  p.tm_s = f.s;
-  f = bh::make_fastdiv(octiles);
-  p.ipt_m = f.m;
-  p.ipt_s = f.s;
-  f = bh::make_fastdiv(OW);
-  p.ow_m = f.m;
-  p.ow_s = f.s;
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_fd(tiles, p.tm_m, p.tm_s);
+  bh::set_fd(octiles, p.ipt_m, p.ipt_s);
+  bh::set_fd(OW, p.ow_m, p.ow_s);
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
-  return bh::launch(ctx, k, dim3(G, 1, 1), dim3(c.NT), args, first, true, "conv_direct");
+  return bh::launch(ctx, k, dim3(G, 1, 1), dim3(c.NT), args, r.first, true, "conv_direct");
 }
 
 }  // namespace bhk

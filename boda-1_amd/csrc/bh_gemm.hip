@@ -719,6 +719,7 @@ void reg_sk_kernels(cfg_t &c) {
 template <int BM, int BN, int NW, int D>
 cfg_t conv_sk_cfg(const char *name) {
   cfg_t c{name, BM, BN, 64, NW * 64, {}};
+  c.family = F_SK;
   reg_sk_kernels<BM, BN, NW, D, A_MVEC, B_IM2COL>(c);
   reg_sk_kernels<BM, BN, NW, D, A_MSCALAR, B_IM2COL>(c);
   reg_sk_kernels<BM, BN, NW, D, A_MVEC, B_IM1X1>(c);
@@ -730,6 +731,7 @@ cfg_t conv_sk_cfg(const char *name) {
 template <int BM, int BN, int NW, int D>
 cfg_t sgemm_sk_cfg(const char *name) {
   cfg_t c{name, BM, BN, 64, NW * 64, {}};
+  c.family = F_SK;
   reg_sk_kernels<BM, BN, NW, D, A_KVEC, B_KVEC>(c);
   reg_sk_kernels<BM, BN, NW, D, A_KSCALAR, B_KSCALAR>(c);
   return c;
@@ -808,11 +810,7 @@ int cfg_index(int op, std::string const &name) {
 
 bool fits_buffer(uint64_t bytes) { return bytes < (uint64_t)OOB - 64; }
 
-void set_fd(uint32_t d, uint32_t &m, uint32_t &s) {
-  bh::fastdiv f = bh::make_fastdiv(d ? d : 1);
-  m = f.m;
-  s = f.s;
-}
+using bh::set_fd;
 
 }  // namespace
 
@@ -891,7 +889,7 @@ void load_tuning() {
 
 // Kernel choice for shapes the tuning table lacks. ring = false: no ring (LDS-DMA, packed
 // bank) config -- launch_conv's fallback when the bank or input is too large for it.
-choice_t heuristic(int op, const uint32_t *d, bool ring = true, bool direct = true) {
+choice_t heuristic(int op, const uint32_t *d, bool ring = true) {
   choice_t ch;
   if (op == 0) {
     // big SGEMMs: the LDS-DMA ring with 128 x 128 tiles, whole K per block (tuned on
@@ -950,18 +948,16 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
   cfg_t const &c = cfgs(op)[ch.cfg];
   p.tiles_m = (p.M + c.BM - 1) / c.BM;
   p.tiles_n = (p.N + c.BN - 1) / c.BN;
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_trace(ctx, p);
   const uint64_t nblk = (uint64_t)p.tiles_m * p.tiles_n;
   if (nblk > 0x7fffffffu) return bh::fail(BH_UNSUP, std::string(what) + ": grid too large");
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const uint32_t ncu = bh::num_cus(ctx);
   p.tbm = c.BM;
   p.tbn = c.BN;
   if (bld == B_IMTAB && !c.k[ald][bld][0]) bld = B_IM2COL;  // table / one-tap loaders: ring kernels only
   if (bld == B_IMTAP && !c.k[ald][bld][0]) bld = B_IMT2;
   if (bld == B_IM1X1S && !c.k[ald][bld][0]) bld = B_IM1X1;
-  if (c.gv) {
+  if (is_gv(c)) {
     // filter-streaming kernel (bh_gv.hip): one block per (64-row tile, K chunk); the K chunks
     // of a tile are combined by its last arriver. ch.splits = K chunks (0: ~1024 blocks)
     kern_t k = c.k[ald][bld][0];
@@ -982,7 +978,7 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
     }
     return bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, true, what);
   }
-  if (c.streamk) {
+  if (c.family == F_STREAMK) {
     // persistent stream-K grid (srk_kernel): ncu x blocks-per-CU blocks share the op's
     // (tile, K tile) iterations equally; ch.splits overrides blocks per CU
     kern_t k = c.k[ald][bld][0];
@@ -1057,15 +1053,20 @@ void conv_dims(const uint32_t *d, uint32_t &M, uint32_t &N, uint32_t &K) {
   K = IC * KY * KX;
 }
 
-std::string describe_cfg(int op, const uint32_t *d, choice_t const &ch);
-std::string describe(int op, const uint32_t *d, choice_t const &ch) {
-  return describe_cfg(op, d, ch) + (ch.wt ? "_wt" : "");
-}
 std::string describe_cfg(int op, const uint32_t *d, choice_t const &ch) {
   cfg_t const &c = cfgs(op)[ch.cfg];
+  switch (c.family) {
+    case F_REF64: return std::string(op == 0 ? "ref64_sgemm" : "ref64_conv") + "_double";
+    case F_DCM: return std::string("mfma32_conv_dm_") + c.name;
+    case F_K1S: case F_K1N: case F_K1D: case F_K1W: case F_K1R: return std::string("mfma32_conv_k1s_") + c.name;
+    case F_WINO: case F_WGX: return std::string("mfma32_conv_wino_") + c.name;
+    case F_DIRECT: return std::string("mfma32_conv_direct_") + c.name;
+    case F_FCV: return std::string("conv_fcv_") + c.name;
+    case F_GV: case F_GVP: case F_GVO: return std::string("mfma16_conv_gv_") + c.name;
+    case F_TILE: case F_SK: case F_RING: case F_STREAMK: break;
+  }
   uint32_t M, N, K;
   std::string s;
-  if (c.ref64) return std::string(op == 0 ? "ref64_sgemm" : "ref64_conv") + "_double";
   if (op == 0) {
     M = d[0]; N = d[1]; K = d[2];
     s = std::string("mfma32_sgemm_") + c.name + ((M % 4 == 0 && N % 4 == 0) ? "_vec" : "_scalar");
@@ -1074,13 +1075,7 @@ std::string describe_cfg(int op, const uint32_t *d, choice_t const &ch) {
     bool k1 = d[5] == 1 && d[6] == 1 && d[7] == 1 && d[8] == 1 && d[9] == 0 && d[10] == 0;
     s = std::string("mfma32_conv_") + (k1 ? "1x1_" : "im2col_") + c.name + ((K % 4 == 0) ? "_avec" : "_ascalar");
   }
-  if (c.streamk) return s + "_streamk";
-  if (c.dc == 2) return std::string("mfma32_conv_dm_") + c.name;
-  if (c.dc == 3) return std::string("mfma32_conv_k1s_") + c.name;
-  if (c.dc == 4 || c.dc == 5) return std::string("mfma32_conv_wino_") + c.name;
-  if (c.dc) return std::string("mfma32_conv_direct_") + c.name;
-  if (c.fcv) return std::string("conv_fcv_") + c.name;
-  if (c.gv) return std::string("mfma16_conv_gv_") + c.name;
+  if (c.family == F_STREAMK) return s + "_streamk";
   uint32_t S = resolve_splits(c, ch, M, N, K, 256);
   if (S > 1) {
     uint64_t nblk = (uint64_t)((M + c.BM - 1) / c.BM) * ((N + c.BN - 1) / c.BN);
@@ -1089,6 +1084,9 @@ std::string describe_cfg(int op, const uint32_t *d, choice_t const &ch) {
     s += red == 1 ? "_splitk_reduce" : "_splitk_inkernel";  // one name per kernel instantiation
   }
   return s;
+}
+std::string describe(int op, const uint32_t *d, choice_t const &ch) {
+  return describe_cfg(op, d, ch) + (ch.wt ? "_wt" : "");
 }
 
 }  // namespace
@@ -1104,7 +1102,7 @@ std::string conv_variant(const uint32_t *d) { return describe(1, d, choose(nullp
 
 uint32_t conv_route_banks(bh_ctx *ctx, const uint32_t *d) {
   choice_t ch = choose(ctx, 1, d);
-  return cfgs(1)[ch.cfg].packA ? bhk::route_bank(cfgs(1)[ch.cfg], d[5], d[6]) : 0u;
+  return bhk::route_bank(cfgs(1)[ch.cfg], d[5], d[6]);
 }
 
 std::string sgemm_variant_ctx(bh_ctx *ctx, uint32_t M, uint32_t N, uint32_t K) {
@@ -1152,166 +1150,178 @@ int launch_sgemm(bh_ctx *ctx, const float *a, const float *b, float *c, uint32_t
   uint32_t d[3] = {M, N, K};
   choice_t ch = choose(ctx, 0, d);
   p.wt = ch.wt && fits_buffer((uint64_t)M * N * 4);
-  if (getenv("BH_EXP_RING_DWORD_B") && vec && cfgs(0)[ch.cfg].k[A_KSCALAR][B_KSCALAR][0])  // experiment
+  const cfg_t &cf = cfgs(0)[ch.cfg];
+  if (getenv("BH_EXP_RING_DWORD_B") && vec && cf.k[A_KSCALAR][B_KSCALAR][0])  // experiment
     return launch_gemm(ctx, 0, ch, A_KSCALAR, B_KSCALAR, p, "sgemm");
-  if (cfgs(0)[ch.cfg].ref64) return launch_ref64_sgemm(ctx, p);
-  if (!vec && (!cfgs(0)[ch.cfg].k[A_KSCALAR][B_KSCALAR][0] || cfgs(0)[ch.cfg].name[0] == 'r')) ch = heuristic(0, d, false);
+  if (cf.family == F_REF64) return launch_ref64_sgemm(ctx, p);
+  if (!vec && (!cf.k[A_KSCALAR][B_KSCALAR][0] || cf.family == F_RING)) ch = heuristic(0, d, false);
   return launch_gemm(ctx, 0, ch, vec ? A_KVEC : A_KSCALAR, vec ? B_KVEC : B_KSCALAR, p, "sgemm");
 }
 
-int launch_conv(bh_ctx *ctx, const float *in, const float *filts, const float *packed, const float *biases, float *out, uint32_t B,
-                uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX, uint32_t sy,
-                uint32_t sx, uint32_t py, uint32_t px, int relu, uint32_t out_ctot, const float *res,
-                bool no_dc, bool repacked, uint32_t pk_banks) {
-  // repacked: a fallback call after this call's filter repack was already dispatched (that repack
-  // recorded the call's start event; no kernel of the fallback may record it again)
-  // out_ctot: channels of the tensor `out` points into (0: OC). Every conv epilogue addresses
-  // image i of the output at i * OCOHW, so a conv can write its channel slab of a wider
-  // tensor (a Concat's output) in place.
-  if (!out_ctot) out_ctot = OC;
-  const uint32_t OH = (H + 2 * py - KY) / sy + 1, OW = (W + 2 * px - KX) / sx + 1;
-  const uint64_t K = (uint64_t)IC * KY * KX, P = (uint64_t)B * OH * OW;
-  const uint64_t in_bytes = (uint64_t)B * IC * H * W * 4, w_bytes = (uint64_t)OC * K * 4;
-  if (!fits_buffer(in_bytes) || !fits_buffer(w_bytes) || !fits_buffer((uint64_t)B * out_ctot * OH * OW * 4))
-    return fail(BH_UNSUP, "conv: tensor larger than 2 GiB");
-  if (K >= (1u << 31) || P >= (1u << 31)) return fail(BH_UNSUP, "conv: GEMM extent too large");
+}  // namespace bh
+
+namespace {
+
+// The implicit-GEMM view of a conv call over the bank in its reference layout (the kernels' common
+// argument block; a route over the packed bank re-points a / lda / a_bytes).
+GemmArgs conv_args(const bh::conv_call &cc, int wt) {
+  const uint64_t K = (uint64_t)cc.IC * cc.KY * cc.KX;
   GemmArgs p{};
-  p.a = filts; p.b = in; p.c = out; p.bias = biases; p.res = res;
-  p.M = OC; p.N = (uint32_t)P; p.K = (uint32_t)K;
+  p.a = cc.filts; p.b = cc.in; p.c = cc.out; p.bias = cc.biases; p.res = cc.res;
+  p.M = cc.OC; p.N = cc.B * cc.OH * cc.OW; p.K = (uint32_t)K;
   p.lda = (uint32_t)K; p.ldb = 0; p.ldc = 0;
-  p.a_bytes = (uint32_t)w_bytes;
-  p.b_bytes = (uint32_t)in_bytes;
-  p.relu = relu;
+  p.a_bytes = (uint32_t)(cc.OC * K * 4);
+  p.b_bytes = (uint32_t)((uint64_t)cc.B * cc.IC * cc.H * cc.W * 4);
+  p.relu = cc.relu;
   // output (and residual) rows take float4 accesses (dword-aligned tensors: any OH*OW; a quad
   // of columns running past its image is stored element by element)
-  p.cvec = ((uintptr_t)out % 4 == 0) && ((uintptr_t)res % 4 == 0);
-  p.H = H; p.W = W; p.KX = KX; p.KYX = KY * KX;
-  p.sy = sy; p.sx = sx; p.py = py; p.px = px;
-  p.OW = OW; p.OHW = OH * OW; p.HW = H * W; p.ICHW = IC * H * W; p.OCOHW = out_ctot * OH * OW;
+  p.cvec = ((uintptr_t)cc.out % 4 == 0) && ((uintptr_t)cc.res % 4 == 0);
+  p.H = cc.H; p.W = cc.W; p.KX = cc.KX; p.KYX = cc.KY * cc.KX;
+  p.sy = cc.sy; p.sx = cc.sx; p.py = cc.py; p.px = cc.px;
+  p.OW = cc.OW; p.OHW = cc.OH * cc.OW; p.HW = cc.H * cc.W; p.ICHW = cc.IC * cc.H * cc.W;
+  p.OCOHW = cc.out_ctot * cc.OH * cc.OW;
   set_fd(p.KYX, p.kyx_m, p.kyx_s);
-  set_fd(KX, p.kx_m, p.kx_s);
+  set_fd(cc.KX, p.kx_m, p.kx_s);
   set_fd(p.OHW, p.ohw_m, p.ohw_s);
-  set_fd(OW, p.ow_m, p.ow_s);
-  const bool k1 = KY == 1 && KX == 1 && sy == 1 && sx == 1 && py == 0 && px == 0;
-  const bool k1v = k1 && (H * W) % 4 == 0 && ((uintptr_t)in % 16 == 0);
-  const bool avec = (K % 4 == 0) && ((uintptr_t)filts % 16 == 0);
-  uint32_t d[11] = {B, IC, H, W, OC, KY, KX, sy, sx, py, px};
-  choice_t ch = choose(ctx, 1, d);
-  p.wt = ch.wt;  // the output fits a 2 GiB buffer (checked above)
-  if (no_dc && cfgs(1)[ch.cfg].dc) ch = heuristic(1, d, true, false);
-  const bool first = !repacked;
-  if (cfgs(1)[ch.cfg].ref64) {  // the double-accumulating known-good kernel (reference layouts)
-    p.IC = IC;
-    return launch_ref64_conv(ctx, p, B, KY, first);
+  set_fd(cc.OW, p.ow_m, p.ow_s);
+  p.wt = wt;  // the output fits a 2 GiB buffer (launch_conv checks)
+  return p;
+}
+
+// Few output columns: a gv family streaming the bank in its reference layout; the window covering the
+// whole unpadded input makes the im2col the input itself (B_FC, 16-B loads). Shape mismatches are
+// UNSUP; a shape the config serves with only a pointer misaligned for its vector loads falls back to
+// the plain gv kernel (input) or the tile kernel (bank): BH_OK with *tile set, nothing launched.
+int launch_gv_ref(bh_ctx *ctx, const choice_t &ch, const bh::conv_call &cc, GemmArgs &p, bool k1, bool avec,
+                  bool first, bool *tile) {
+  const cfg_t &c = cfgs(1)[ch.cfg];
+  const bool fc_shape = cc.OH == 1 && cc.OW == 1 && cc.KY == cc.H && cc.KX == cc.W && cc.py == 0 && cc.px == 0;
+  const bool in16 = (uintptr_t)cc.in % 16 == 0, fc = fc_shape && in16;
+  // 16-B loads of the bank (K % 4 or pointer) or of the input impossible
+  auto to_tile = [&] {
+    *tile = true;
+    return BH_OK;
+  };
+  *tile = false;
+  if (c.family == F_FCV) {
+    // batch-streaming ipconv (bh_gv.hip fcv_kernel): a wave per BM / 4 bank rows
+    if (!fc_shape || p.K % 4 || cc.B > (uint32_t)c.BN)
+      return bh::fail(BH_UNSUP, "conv: fcv configs need an ipconv (window = the whole unpadded input) at batch <= " +
+                                    std::to_string(c.BN) + " with K % 4 == 0");
+    if (!(fc && avec)) return to_tile();
+    void *args[] = {&p};
+    return bh::launch(ctx, (const void *)c.k[A_MVEC][B_FC][0], dim3((cc.OC + c.BM - 1) / c.BM), dim3(c.NT), args, first,
+                      true, "conv");
   }
-  if (cfgs(1)[ch.cfg].gv && !cfgs(1)[ch.cfg].packA) {
-    // few output columns: stream the bank in its reference layout; the window covering the
-    // whole unpadded input makes the im2col the input itself (B_FC, 16-B loads). Shape
-    // mismatches are UNSUP; a shape the config serves with only a pointer misaligned for its
-    // vector loads falls back to the plain gv kernel (input) or the tile kernel (bank)
-    const bool fc_shape = OH == 1 && OW == 1 && KY == H && KX == W && py == 0 && px == 0;
-    const bool in16 = (uintptr_t)in % 16 == 0, fc = fc_shape && in16;
-    bool tile_fallback = !avec;
-    if (cfgs(1)[ch.cfg].fcv) {
-      // batch-streaming ipconv (bh_gv.hip fcv_kernel): a wave per BM / 4 bank rows
-      const cfg_t &fc_c = cfgs(1)[ch.cfg];
-      if (!fc_shape || K % 4 || B > (uint32_t)fc_c.BN)
-        return fail(BH_UNSUP, "conv: fcv configs need an ipconv (window = the whole unpadded input) at batch <= " +
-                                  std::to_string(fc_c.BN) + " with K % 4 == 0");
-      if (fc && avec) {
-        void *args[] = {&p};
-        return bh::launch(ctx, (const void *)fc_c.k[A_MVEC][B_FC][0], dim3((OC + fc_c.BM - 1) / fc_c.BM), dim3(fc_c.NT),
-                          args, first, true, "conv");
-      }
-      tile_fallback = true;  // 16-B loads of the bank or the input rows impossible
-    } else if (cfgs(1)[ch.cfg].k[A_MVEC][B_IM1X1S][0]) {
-      // gvo (bh_gv.hip): 1x1 over the reference-layout bank, 16-deep k groups; an ipconv takes
-      // its input rows as the columns (B_FC, one 16-B load per column tile and k group)
-      const int cx = cfgs(1)[ch.cfg].gv_cx;
-      if (fc_shape && K % 16 == 0 && cfgs(1)[ch.cfg].k[A_MVEC][B_FC][0]) {
-        if (fc && avec) return launch_gemm(ctx, 1, ch, A_MVEC, B_FC, p, "conv", first);
-        tile_fallback = true;
-      } else {
-        if (!k1 || IC % 16) return fail(BH_UNSUP, "conv: gvo configs need a 1x1 conv with IC % 16 == 0");
-        if ((OH * OW) % (uint32_t)cx) return fail(BH_UNSUP, "conv: interleaved-column configs need OH*OW % run == 0");
-        if (avec && (uintptr_t)in % (4u * cx) == 0) return launch_gemm(ctx, 1, ch, A_MVEC, B_IM1X1S, p, "conv", first);
-        tile_fallback = true;  // 16-B bank rows or CX-wide pixel runs of the input misaligned
-      }
-    } else if (avec) {
-      return launch_gemm(ctx, 1, ch, A_MVEC, fc ? B_FC : (k1 ? B_IM1X1 : B_IM2COL), p, "conv", first);
-    }
-    if (tile_fallback) {
-      ch = choice_t{};  // unaligned bank (K % 4 or pointer) or input: a tile kernel
-      ch.cfg = cfg_index(1, "128x32x32");
-      ch.red = 1;
-    }
-  }
-  if (cfgs(1)[ch.cfg].packA) {
-    // ring kernels read the filter bank k-major: repack it first (this call's first dispatch)
-    // (K order (ky, kx, ic), rows padded to a multiple of 64; input offsets + 2^30 must miss).
-    // A Winograd route reads its bank behind it: from the caller's pack when that holds the bank
-    // (pk_banks), otherwise from a pack of just the k-major bank + that bank made here. The 2 GiB
-    // check and the context's pack buffer are sized by what the route reads.
-    const uint32_t need = route_bank(cfgs(1)[ch.cfg], KY, KX);
-    pk_banks &= all_banks(KY, KX);
-    const uint32_t oc4 = (OC + 3) & ~3u, kp = (uint32_t)(kmajor_floats(OC, IC, KY, KX) / oc4);
-    const float *wp = packed;
-    uint32_t banks = pk_banks;
-    if (wp && need && !(pk_banks & need)) wp = nullptr;  // the caller's pack lacks the route's bank
-    if (!wp) banks = need;
-    if (banks_floats(OC, IC, KY, KX, need) * 4 >= 0x7fffffc0ull || in_bytes >= (1ull << 30)) {
-      ch = heuristic(1, d, false);
+  int bld = fc ? B_FC : (k1 ? B_IM1X1 : B_IM2COL);
+  if (c.family == F_GVO) {
+    // 1x1 over the reference-layout bank, 16-deep k groups; an ipconv takes its input rows as the
+    // columns (B_FC, one 16-B load per column tile and k group)
+    if (fc_shape && p.K % 16 == 0 && c.k[A_MVEC][B_FC][0]) {
+      if (!fc) return to_tile();
     } else {
-      bool rp = repacked;  // a repack of this call already dispatched (it recorded the start event)
-      if (!wp) {
-        int rc = ensure_wpack(ctx, banks_floats(OC, IC, KY, KX, banks) * 4);
-        if (rc == BH_OK) rc = launch_pack_banks(ctx, filts, (float *)ctx->wpack, OC, IC, KY, KX, banks, first, false);
-        if (rc != BH_OK) return rc;
-        wp = (const float *)ctx->wpack;
-        rp = true;
-      }
-      const bool kfirst = !rp;  // the main kernel is the call's first dispatch
-      p.a = wp;
-      p.lda = oc4;
-      p.a_bytes = kp * oc4 * 4;
-      p.IC = IC;
-      set_fd(IC, p.ic_m, p.ic_s);
-      if (cfgs(1)[ch.cfg].dc) {
-        const cfg_t &dcc = cfgs(1)[ch.cfg];
-        const int rc = dcc.dc == 2   ? launch_dcm(ctx, dcc, p, B, KY, KX, sy, sx, ch.splits, kfirst)
-                       : dcc.dc == 3 ? launch_k1s(ctx, dcc, p, B, KY, KX, sy, sx, ch.splits, kfirst)
-                       : dcc.dc == 4 ? (need
-                                            ? launch_wg(ctx, dcc, wp + bank_offset(OC, IC, KY, KX, banks, need), in, biases, res,
-                                                        out, out_ctot, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, p.wt,
-                                                        ch.splits, kfirst)
-                                            : bh::fail(BH_UNSUP, std::string("conv: ") + dcc.name + " is for 3x3 convs"))
-                       : dcc.dc == 5 ? (need
-                                            ? launch_wgx(ctx, dcc, wp + bank_offset(OC, IC, KY, KX, banks, need), in, biases,
-                                                         res, out, out_ctot, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu,
-                                                         p.wt, ch.splits, kfirst)
-                                            : bh::fail(BH_UNSUP, std::string("conv: ") + dcc.name + " is for other kernel sizes"))
-                                     : launch_dc(ctx, dcc, p, B, KY, KX, sy, sx, kfirst);
-        if (rc != BH_UNSUP || (ctx && ctx->ovr_cfg[1] >= 0)) return rc;
-        return launch_conv(ctx, in, filts, wp, biases, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, out_ctot,
-                           res, true, rp, banks);
-      }
-      if (cfgs(1)[ch.cfg].gv) {
-        // register streaming over the packed bank (bh_gv.hip gvp_kernel): 16-deep k groups
-        // inside one filter tap
-        if (IC % 16) return fail(BH_UNSUP, "conv: gvp configs need IC % 16 == 0");
-        if (cfgs(1)[ch.cfg].gv_cx > 1 && (!k1 || (OH * OW) % (uint32_t)cfgs(1)[ch.cfg].gv_cx))
-          return fail(BH_UNSUP, "conv: interleaved-column configs need a 1x1 conv with OH*OW % run == 0");
-        return launch_gemm(ctx, 1, ch, A_KVEC, k1 ? B_IM1X1S : B_IMTAP, p, "conv", kfirst);
-      }
-      const uint32_t bk = (uint32_t)cfgs(1)[ch.cfg].BK;
-      const bool tab = ((p.K + bk - 1) / bk) * bk <= (uint32_t)TAB_MAX;  // K rows a block tabulates
-      const int bld = k1 ? (IC % bk == 0 ? B_IM1X1S : B_IM1X1)
-                         : (IC >= bk ? (IC % bk == 0 ? B_IMTAP : B_IMT2) : (tab ? B_IMTAB : B_IM2COL));
-      return launch_gemm(ctx, 1, ch, A_KVEC, bld, p, "conv", kfirst);
+      if (!k1 || cc.IC % 16) return bh::fail(BH_UNSUP, "conv: gvo configs need a 1x1 conv with IC % 16 == 0");
+      if ((cc.OH * cc.OW) % (uint32_t)c.cx)
+        return bh::fail(BH_UNSUP, "conv: interleaved-column configs need OH*OW % run == 0");
+      if ((uintptr_t)cc.in % (4u * c.cx)) return to_tile();  // CX-wide pixel runs of the input misaligned
+      bld = B_IM1X1S;
     }
   }
-  return launch_gemm(ctx, 1, ch, avec ? A_MVEC : A_MSCALAR, k1v ? B_IM1X1V : (k1 ? B_IM1X1 : B_IM2COL), p, "conv",
-                     first);
+  if (!avec) return to_tile();
+  return launch_gemm(ctx, 1, ch, A_MVEC, bld, p, "conv", first);
+}
+
+}  // namespace
+
+namespace bh {
+
+int launch_conv(bh_ctx *ctx, const conv_call &cc) {
+  const uint32_t B = cc.B, IC = cc.IC, H = cc.H, W = cc.W, OC = cc.OC, KY = cc.KY, KX = cc.KX;
+  const uint64_t K = (uint64_t)IC * KY * KX, P = (uint64_t)B * cc.OH * cc.OW;
+  const uint64_t in_bytes = (uint64_t)B * IC * H * W * 4, w_bytes = (uint64_t)OC * K * 4;
+  if (!fits_buffer(in_bytes) || !fits_buffer(w_bytes) || !fits_buffer((uint64_t)B * cc.out_ctot * cc.OH * cc.OW * 4))
+    return fail(BH_UNSUP, "conv: tensor larger than 2 GiB");
+  if (K >= (1u << 31) || P >= (1u << 31)) return fail(BH_UNSUP, "conv: GEMM extent too large");
+  const bool k1 = KY == 1 && KX == 1 && cc.sy == 1 && cc.sx == 1 && cc.py == 0 && cc.px == 0;
+  const bool k1v = k1 && (H * W) % 4 == 0 && ((uintptr_t)cc.in % 16 == 0);
+  const bool avec = (K % 4 == 0) && ((uintptr_t)cc.filts % 16 == 0);
+  const uint32_t d[11] = {B, IC, H, W, OC, KY, KX, cc.sy, cc.sx, cc.py, cc.px};
+  choice_t ch = choose(ctx, 1, d);
+  const GemmArgs args0 = conv_args(cc, ch.wt);
+  // a tile kernel over the bank in its reference layout: serves every shape
+  auto tile = [&](const choice_t &t, GemmArgs &p, bool first) {
+    return launch_gemm(ctx, 1, t, avec ? A_MVEC : A_MSCALAR, k1v ? B_IM1X1V : (k1 ? B_IM1X1 : B_IM2COL), p, "conv", first);
+  };
+  // State of the attempts. A repack of this call, once dispatched, has recorded the call's start
+  // event: no kernel after it may record it again. A second attempt reuses the pack in hand.
+  bool repacked = false;
+  const float *pack = cc.packed;                            // the pack in hand (null: none yet)
+  uint32_t pack_banks = cc.pk_banks & all_banks(KY, KX);    // the Winograd banks it holds
+  for (;;) {
+    const cfg_t &c = cfgs(1)[ch.cfg];
+    GemmArgs p = args0;
+    const bool first = !repacked;
+    if (c.family == F_REF64) {  // the double-accumulating known-good kernel (reference layouts)
+      p.IC = IC;
+      return launch_ref64_conv(ctx, p, B, KY, first);
+    }
+    if (c.family == F_GV || c.family == F_GVO || c.family == F_FCV) {
+      bool to_tile = false;
+      const int rc = launch_gv_ref(ctx, ch, cc, p, k1, avec, first, &to_tile);
+      if (!to_tile) return rc;
+      choice_t t;
+      t.cfg = cfg_index(1, "128x32x32");
+      t.red = 1;
+      return tile(t, p, first);
+    }
+    if (!c.packA) return tile(ch, p, first);
+    // The family reads the filter bank k-major: repack it first (this call's first dispatch)
+    // (K order (ky, kx, ic), rows padded to a multiple of 64; input offsets + 2^30 must miss).
+    // A Winograd route reads its bank behind it: from the pack in hand when that holds the bank,
+    // otherwise from a pack of just the k-major bank + that bank made here. The 2 GiB check and the
+    // context's pack buffer are sized by what the route reads.
+    const uint32_t need = route_bank(c, KY, KX);
+    if (pack && need && !(pack_banks & need)) pack = nullptr;  // the pack in hand lacks the route's bank
+    if (!pack) pack_banks = need;
+    if (banks_floats(OC, IC, KY, KX, need) * 4 >= 0x7fffffc0ull || in_bytes >= (1ull << 30))
+      return tile(heuristic(1, d, false), p, first);
+    if (!pack) {
+      int rc = ensure_wpack(ctx, banks_floats(OC, IC, KY, KX, pack_banks) * 4);
+      if (rc == BH_OK) rc = launch_pack_banks(ctx, cc.filts, (float *)ctx->wpack, OC, IC, KY, KX, pack_banks, first, false);
+      if (rc != BH_OK) return rc;
+      pack = (const float *)ctx->wpack;
+      repacked = true;
+    }
+    const bool kfirst = !repacked;  // the main kernel is the call's first dispatch
+    const uint32_t oc4 = (OC + 3) & ~3u, kp = (uint32_t)(kmajor_floats(OC, IC, KY, KX) / oc4);
+    p.a = pack;
+    p.lda = oc4;
+    p.a_bytes = kp * oc4 * 4;
+    p.IC = IC;
+    set_fd(IC, p.ic_m, p.ic_s);
+    if (c.launch) {
+      const route_t r{need ? pack + bank_offset(OC, IC, KY, KX, pack_banks, need) : nullptr, ch.splits, p.wt, kfirst};
+      const int rc = c.launch(ctx, c, cc, p, r);
+      // with an override set, BH_UNSUP is the answer; otherwise the heuristic's choice (never a
+      // direct family: the loop ends there) serves the shape, from the pack in hand
+      if (rc != BH_UNSUP || (ctx && ctx->ovr_cfg[1] >= 0)) return rc;
+      ch = heuristic(1, d);
+      continue;
+    }
+    if (c.family == F_GVP) {
+      // register streaming over the packed bank (bh_gv.hip gvp_kernel): 16-deep k groups
+      // inside one filter tap
+      if (IC % 16) return fail(BH_UNSUP, "conv: gvp configs need IC % 16 == 0");
+      if (c.cx > 1 && (!k1 || (cc.OH * cc.OW) % (uint32_t)c.cx))
+        return fail(BH_UNSUP, "conv: interleaved-column configs need a 1x1 conv with OH*OW % run == 0");
+      return launch_gemm(ctx, 1, ch, A_KVEC, k1 ? B_IM1X1S : B_IMTAP, p, "conv", kfirst);
+    }
+    const uint32_t bk = (uint32_t)c.BK;
+    const bool tab = ((p.K + bk - 1) / bk) * bk <= (uint32_t)TAB_MAX;  // K rows a block tabulates
+    const int bld = k1 ? (IC % bk == 0 ? B_IM1X1S : B_IM1X1)
+                       : (IC >= bk ? (IC % bk == 0 ? B_IMTAP : B_IMT2) : (tab ? B_IMTAB : B_IM2COL));
+    return launch_gemm(ctx, 1, ch, A_KVEC, bld, p, "conv", kfirst);
+  }
 }
 
 }  // namespace bh

@@ -357,27 +357,65 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, const float *lds
 
 typedef void (*kern_t)(GemmArgs);
 
+// What launch_conv / launch_gemm do with a configuration.
+enum family_t {
+  F_TILE,     // register-staged tile kernels (bh_gemm.hip gemm_kernel)
+  F_SK,       // small-K latency kernels (bh_gemm.hip gemm_sk_kernel): dispatched as F_TILE
+  F_RING,     // LDS-DMA ring kernels (bh_ring.hip); conv ones read the packed bank
+  F_STREAMK,  // the ring as a persistent stream-K grid (srk_kernel): k[..][..][0] only
+  // filter-streaming kernels (bh_gv.hip): grid (M / BM) x K chunks, BN >= N
+  F_GV,   // over the bank in its reference layout
+  F_GVP,  // over the packed bank, 16-deep k groups inside one filter tap
+  F_GVO,  // 1x1 / ipconv over the reference-layout bank, 16-deep k groups
+  F_FCV,  // batch-streaming ipconv (fcv_kernel), batch <= BN
+  // direct families: cfg_t::launch dispatches them, BH_UNSUP falls back to the heuristic's choice
+  F_DIRECT,  // bh_direct.hip
+  F_DCM,     // bh_dcm.hip
+  F_K1S, F_K1N, F_K1D, F_K1W, F_K1R,  // bh_k1s.hip: the forms of the resident-bank 1x1 kernel
+  F_WINO,    // bh_wino.hip
+  F_WGX,     // bh_wgx.hip
+  F_REF64,   // double-accumulating known-good kernel (bh_ref64.hip), never tuned in
+};
+
+// What launch_conv has resolved for a direct family's launcher.
+struct route_t {
+  const float *bank;  // the Winograd bank the configuration reads (null: it has none for this kernel size)
+  uint32_t splits;    // the choice's splits (each family's own grid modes)
+  int wt;             // output stores write through
+  bool first;         // the launch is the call's first dispatch
+};
+struct cfg_t;
+// p: filled by launch_conv with a = the packed k-major bank
+typedef int (*conv_launch_t)(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
+
 struct cfg_t {
   const char *name;
   int BM, BN, BK, NT;
   kern_t k[4][NBLD][3];  // [A loader][B loader][SPL]
-  int packA;          // conv: A is the filter bank repacked k-major [K][OC4] (bh_ring.hip)
-  int streamk = 0;    // persistent stream-K grid (srk_kernel): k[..][..][0] only
-  int lds_bytes = 0;  // static LDS per block (stream-K grid sizing)
-  int gv = 0;         // filter-streaming kernel (bh_gv.hip): grid (M / BM) x K chunks, BN >= N
-  int dc_icmax = 0;   // dc == 1 resident-weight form: input channels it keeps resident (0: the ring form)
-  int dc = 0;         // direct conv (bh_direct.hip; 2: bh_dcm.hip, 3: bh_k1s.hip): kernel dc_ky x dc_kx, stride dc_s, strip dc_rin x dc_wpm
-  int dc_ky = 0, dc_kx = 0, dc_s = 0, dc_wpm = 0, dc_rin = 0;
-  int dc_ci = 0;      // dc == 2 (bh_dcm.hip): input channels per stage
-  int gv_cx = 1;      // gv: interleaved column tiles (1x1, a lane's gv_cx pixels per load)
-  int fcv = 0;        // gv: batch-streaming ipconv kernel (bh_gv.hip fcv_kernel), batch <= BN
-  int ref64 = 0;      // double-accumulating known-good kernel (bh_ref64.hip), never tuned in
-  int k1n = 0;        // dc == 3: the pixels-on-N form (bh_k1s.hip k1n_kernel; gv_cx pixels per lane)
-  int k1d = 0;        // dc == 3: the whole bank resident, input by 16-B LDS-DMA (bh_k1s.hip k1d_kernel)
-  int k1w = 0;        // dc == 3: store waves of the k1w form (bh_k1s.hip k1w_kernel; NT counts them too)
-  int k1w_sl = 0;     // k1w: LDS staging slots per compute wave
-  int k1r = 0;        // dc == 3: the bank slice in VGPRs, K <= k1r (bh_k1s.hip k1r_kernel)
+  int packA;             // conv: A is the filter bank repacked k-major [K][OC4] (bh_ring.hip)
+  family_t family = F_TILE;
+  conv_launch_t launch = nullptr;  // direct families: set where the family's configs are built
+  int lds_bytes = 0;  // F_STREAMK: static LDS per block (grid sizing)
+  int cx = 1;         // gv families: interleaved column tiles (1x1, a lane's cx pixels per load)
+  // ---- direct families: the kernel size the configuration is built for, then each family's own
+  int ky = 0, kx = 0;
+  uint32_t bank = 0;   // F_WINO / F_WGX: the Winograd bank (BANK_*) read behind the k-major bank
+  int stride = 0;      // F_DIRECT
+  int wpm = 0;         // F_DIRECT / F_DCM: strip pitch (floats)
+  int strip_rows = 0;  // F_DIRECT / F_DCM: input rows a strip holds
+  int v4 = 0;          // F_DIRECT / F_DCM / F_WINO: 16-B strip pieces (rows of W % 4 == 0)
+  int icmax = 0;       // F_DIRECT resident-weight form: input channels it keeps resident (0: the ring form)
+  int kc = 0;          // F_DCM / F_K1*: input channels per stage
+  int q = 0;           // F_K1*: ring depth (chunks of kc channels; F_K1D: ring slots D)
+  int tn = 1;          // F_K1N: pixels per lane
+  int store_waves = 0, stage_slots = 0;  // F_K1W: store waves (NT counts them too), LDS staging slots per compute wave
+  int kmax = 0;        // F_K1R: the largest K its registers hold
+  int slots = 0;       // F_WINO: strip slots
+  int sp = 0;          // F_WINO / F_WGX: strip DMA pieces per thread and stage
+  int mo = 0;          // F_WGX: output tile (the form F(mo x mo, ky x kx))
+  int sk = 0;          // F_WGX: 1: persistent stream-K grid, 2 / 3: whole units + a split tail
 };
+inline bool is_gv(const cfg_t &c) { return c.family >= F_GV && c.family <= F_FCV; }
 
 // bh_ring.hip: LDS-DMA ring configurations (conv ones read the repacked filter bank) and
 // the repack itself (into the context's wpack buffer; first dispatch of a conv call)
@@ -390,31 +428,17 @@ std::vector<cfg_t> dc_cfgs();
 std::vector<cfg_t> ref64_cfgs();
 int launch_ref64_conv(bh_ctx *ctx, GemmArgs &p, uint32_t B, uint32_t KY, bool first);
 int launch_ref64_sgemm(bh_ctx *ctx, GemmArgs &p);
-int launch_dc(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-              uint32_t sx, bool first);
 // bh_dcm.hip: multi-channel direct-conv configurations for stride-1 3x3 / 5x5 convs
 std::vector<cfg_t> dcm_cfgs();
-int launch_dcm(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-               uint32_t sx, uint32_t splits, bool first);
 // bh_k1s.hip: 1x1 convs with the bank slice resident in LDS, input streamed into registers
 std::vector<cfg_t> k1s_cfgs();
-int launch_k1s(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-               uint32_t sx, uint32_t splits, bool first);
-// bh_wino.hip: Winograd F(2x2, 3x3) configurations for stride-1 3x3 convs; u = the Winograd bank
-// (the part of a 3x3 pack behind the k-major bank)
+// bh_wino.hip: Winograd F(2x2, 3x3) configurations for stride-1 3x3 convs (route_t::bank: the part of a
+// 3x3 pack behind the k-major bank)
 std::vector<cfg_t> wg_cfgs();
-int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, const float *bias, const float *res,
-              float *out, uint32_t out_ctot, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
-              uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu, int wt, uint32_t splits,
-              bool first);
 size_t wino_bank_floats(uint32_t OC, uint32_t IC);
-// bh_wgx.hip: position-split Winograd (F(4x4,3x3), F(2x2,5x5), F(2x2,3x3); two waves per SIMD); u = the
-// bank of the configuration's form (wgx_bank_offset into a pack)
+// bh_wgx.hip: position-split Winograd (F(4x4,3x3), F(2x2,5x5), F(2x2,3x3); two waves per SIMD);
+// route_t::bank: the bank of the configuration's form
 std::vector<cfg_t> wgx_cfgs();
-int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, const float *bias, const float *res,
-               float *out, uint32_t out_ctot, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
-               uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu, int wt, uint32_t splits,
-               bool first);
 size_t wx_bank_floats(uint32_t OC, uint32_t IC);
 int launch_wx_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uint32_t IC, uint32_t R, bool first,
                    bool last);
@@ -427,8 +451,10 @@ uint32_t all_banks(uint32_t KY, uint32_t KX);
 size_t banks_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX, uint32_t banks);
 // offset in floats of bank (one BANK_*) in a pack holding banks (it must be one of them)
 size_t bank_offset(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX, uint32_t banks, uint32_t bank);
-// the bank a configuration reads (0: the k-major bank only)
-uint32_t route_bank(const cfg_t &c, uint32_t KY, uint32_t KX);
+// the bank a configuration reads on a KY x KX conv (0: the k-major bank only)
+inline uint32_t route_bank(const cfg_t &c, uint32_t KY, uint32_t KX) {
+  return (uint32_t)c.ky == KY && (uint32_t)c.kx == KX ? c.bank : 0;
+}
 int launch_pack_banks(bh_ctx *ctx, const float *filts, float *packed, uint32_t OC, uint32_t IC, uint32_t KY,
                       uint32_t KX, uint32_t banks, bool first, bool last);
 int launch_wino_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uint32_t IC, bool first, bool last);

@@ -522,7 +522,7 @@ __global__ __launch_bounds__(NW * 64) void gvp_kernel(GemmArgs p) {
 template <int R, int C, int NW, int NG, int DB>
 cfg_t gv_cfg(const char *name) {
   cfg_t c{name, 16 * R, 16 * C, 16 * NW, NW * 64, {}, 0};  // BK: K granule of a block chunk
-  c.gv = 1;
+  c.family = F_GV;
   c.k[A_MVEC][B_FC][0] = gv_kernel<R, C, NW, NG, DB, B_FC>;
   c.k[A_MVEC][B_IM1X1][0] = gv_kernel<R, C, NW, NG, DB, B_IM1X1>;
   c.k[A_MVEC][B_IM2COL][0] = gv_kernel<R, C, NW, NG, DB, B_IM2COL>;
@@ -598,8 +598,7 @@ __global__ __launch_bounds__(256) void fcv_kernel(GemmArgs p) {
 template <int R, int U, int NB>
 cfg_t fcv_cfg(const char *name) {
   cfg_t c{name, 4 * R, NB, 256 * U, 256, {}, 0};
-  c.gv = 1;
-  c.fcv = 1;
+  c.family = F_FCV;
   c.k[A_MVEC][B_FC][0] = fcv_kernel<R, U, NB>;
   return c;
 }
@@ -608,8 +607,8 @@ cfg_t fcv_cfg(const char *name) {
 template <int R, int C, int NW, int PD, int CX = 1>
 cfg_t gvo_cfg(const char *name) {
   cfg_t c{name, 16 * R, 16 * C, 16 * NW, NW * 64, {}, 0};
-  c.gv = 1;
-  c.gv_cx = CX;
+  c.family = F_GVO;
+  c.cx = CX;
   c.k[A_MVEC][B_IM1X1S][0] = gvp_kernel<R, C, NW, 1, 0, B_IM1X1, PD, CX>;
   if constexpr (CX == 1) c.k[A_MVEC][B_FC][0] = gvp_kernel<R, C, NW, 1, 0, B_FC, PD>;
   return c;
@@ -618,8 +617,8 @@ cfg_t gvo_cfg(const char *name) {
 template <int R, int C, int NW, int PD, int CX>
 cfg_t gvx_cfg(const char *name) {
   cfg_t c{name, 16 * R, 16 * C, 16 * NW, NW * 64, {}, 1};
-  c.gv = 1;
-  c.gv_cx = CX;
+  c.family = F_GVP;
+  c.cx = CX;
   c.k[A_KVEC][B_IM1X1S][0] = gvp_kernel<R, C, NW, 1, 0, B_IM1X1S, PD, CX>;
   return c;
 }
@@ -628,7 +627,7 @@ cfg_t gvx_cfg(const char *name) {
 template <int R, int C, int NW, int NG, int DB, int PD = 0>
 cfg_t gvp_cfg(const char *name) {
   cfg_t c{name, 16 * R, 16 * C, 16 * NW, NW * 64, {}, 1};
-  c.gv = 1;
+  c.family = F_GVP;
   c.k[A_KVEC][B_IMTAP][0] = gvp_kernel<R, C, NW, NG, DB, B_IMTAP, PD>;
   c.k[A_KVEC][B_IM1X1S][0] = gvp_kernel<R, C, NW, NG, DB, B_IM1X1S, PD>;
   return c;

@@ -29,6 +29,7 @@
 #include "bh_gemm_dev.h"
 
 namespace bhk {
+static int launch_k1s(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 namespace {
 
 // DBG (diagnostic builds in the instrumented library only; wrong results by design): bit 0 = no
@@ -718,16 +719,21 @@ __global__ __launch_bounds__(NW * 64) void k1d_kernel(GemmArgs p) {
   vm_wait<0>();
 }
 
+// form: which of the family's kernels; KC-channel chunks, ring depth Q
+void set_k1(cfg_t &c, family_t form, int KC, int Q) {
+  c.family = form;
+  c.launch = launch_k1s;
+  c.ky = 1;
+  c.kx = 1;
+  c.kc = KC;
+  c.q = Q;
+}
+
 template <int TM, int KC, int D, int NW, int DBG = 0>
 cfg_t k1d_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * NW, KC, 64 * NW, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = k1d_kernel<TM, KC, D, NW, DBG>;
-  c.dc = 3;
-  c.dc_ky = 1;
-  c.dc_kx = 1;
-  c.dc_ci = KC;
-  c.dc_rin = D;
-  c.k1d = 1;
+  set_k1(c, F_K1D, KC, D);
   return c;
 }
 
@@ -929,13 +935,9 @@ template <int TM, int KC, int Q, int NW, int NSW, int NSL>
 cfg_t k1w_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * NW, KC, 64 * (NW + NSW), {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = k1w_kernel<TM, KC, Q, NW, NSW, NSL>;
-  c.dc = 3;
-  c.dc_ky = 1;
-  c.dc_kx = 1;
-  c.dc_ci = KC;
-  c.dc_rin = Q;
-  c.k1w = NSW;
-  c.k1w_sl = NSL;
+  set_k1(c, F_K1W, KC, Q);
+  c.store_waves = NSW;
+  c.stage_slots = NSL;
   return c;
 }
 
@@ -1087,12 +1089,8 @@ template <int TM, int KMAX, int KC, int Q, int NW>
 cfg_t k1r_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * NW, KC, 64 * NW, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = k1r_kernel<TM, KMAX, KC, Q, NW>;
-  c.dc = 3;
-  c.dc_ky = 1;
-  c.dc_kx = 1;
-  c.dc_ci = KC;
-  c.dc_rin = Q;
-  c.k1r = KMAX;
+  set_k1(c, F_K1R, KC, Q);
+  c.kmax = KMAX;
   return c;
 }
 
@@ -1100,13 +1098,8 @@ template <int TM, int TN, int KC, int Q, int NW, int DBG = 0>
 cfg_t k1n_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * TN * NW, KC, 64 * NW, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = k1n_kernel<TM, TN, KC, Q, NW, DBG>;
-  c.dc = 3;
-  c.dc_ky = 1;
-  c.dc_kx = 1;
-  c.dc_ci = KC;
-  c.dc_rin = Q;
-  c.gv_cx = TN;
-  c.k1n = 1;
+  set_k1(c, F_K1N, KC, Q);
+  c.tn = TN;
   return c;
 }
 
@@ -1114,11 +1107,7 @@ template <int TM, int KC, int Q, int NW, int DBG = 0>
 cfg_t k1s_cfg(const char *name) {
   cfg_t c{name, 32 * TM, 32 * NW, KC, 64 * NW, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = k1s_kernel<TM, KC, Q, NW, DBG>;
-  c.dc = 3;
-  c.dc_ky = 1;
-  c.dc_kx = 1;
-  c.dc_ci = KC;
-  c.dc_rin = Q;
+  set_k1(c, F_K1S, KC, Q);
   return c;
 }
 
@@ -1187,8 +1176,8 @@ std::vector<cfg_t> k1s_cfgs() {
 // chunks, at least D - 1 of them; OH*OW % 4 == 0 and a 16-B aligned input (16-B DMA pieces of 4 pixels
 // never straddle two images). splits: 0 = as many blocks per CU as fit (at most 4), 1..4 = blocks per
 // CU, 8 = one unit per wave (the whole grid queued)
-int launch_k1d(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t splits, bool first) {
-  const uint32_t KC = (uint32_t)c.dc_ci, D = (uint32_t)c.dc_rin, NW = (uint32_t)c.NT / 64, BM = (uint32_t)c.BM;
+static int launch_k1d(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t splits, bool first) {
+  const uint32_t KC = (uint32_t)c.kc, D = (uint32_t)c.q, NW = (uint32_t)c.NT / 64, BM = (uint32_t)c.BM;
   if (p.K % KC || p.K / KC < D - 1)
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " needs input channels a multiple of " +
                                   std::to_string(KC) + ", at least " + std::to_string((D - 1) * KC));
@@ -1203,23 +1192,17 @@ int launch_k1d(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t splits, bool f
   const uint64_t units = (uint64_t)((p.N + 31) / 32) * ntm;
   if (units >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: k1d grid too large");
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return bh::fail(BH_ERR, "conv: k1d LDS attribute");
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, c.NT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  if (int rc = bh::dyn_lds(k, (uint32_t)lds, "conv: k1d LDS attribute")) return rc;
+  const int occ = bh::occupancy(k, c.NT, (size_t)lds);
   const uint64_t need = (units + NW - 1) / NW;  // blocks for one unit per wave
   uint64_t G = need;
-  if (splits < 8) G = std::min<uint64_t>(need, (uint64_t)ncu * std::min<uint32_t>(splits ? splits : 4, (uint32_t)std::min(occ, 4)));
+  if (splits < 8)
+    G = std::min<uint64_t>(need, (uint64_t)bh::num_cus(ctx) * std::min<uint32_t>(splits ? splits : 4, (uint32_t)std::min(occ, 4)));
   p.tbm = ocp;
   p.tiles_m = ntm;
   p.total_it = (uint32_t)units;
-  bh::fastdiv f = bh::make_fastdiv(ntm);
-  p.tm_m = f.m;
-  p.tm_s = f.s;
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_fd(ntm, p.tm_m, p.tm_s);
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
   return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, first, true, "conv_k1d", (uint32_t)lds);
 }
@@ -1229,68 +1212,61 @@ int launch_k1d(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t splits, bool f
 // of KC channels) and whose bank slice fits the LDS. splits: 0 = two blocks per CU where they
 // fit, 1..4 = blocks per CU (a persistent grid: a wave takes every wg-th unit), 8 = one unit per
 // wave (the whole grid queued: no wave runs two units while another SIMD idles in the tail).
-int launch_k1s(bh_ctx *ctx, const cfg_t &c, GemmArgs &p, uint32_t B, uint32_t KY, uint32_t KX, uint32_t sy,
-               uint32_t sx, uint32_t splits, bool first) {
-  (void)B;
-  if (KY != 1 || KX != 1 || sy != 1 || sx != 1 || p.py || p.px)
+static int launch_k1s(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r) {
+  if (cc.KY != 1 || cc.KX != 1 || cc.sy != 1 || cc.sx != 1 || p.py || p.px)
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for unpadded stride-1 1x1 convs");
-  const uint32_t KC = (uint32_t)c.dc_ci, Q = (uint32_t)c.dc_rin, NT = (uint32_t)c.NT;
-  if (c.k1d) return launch_k1d(ctx, c, p, splits, first);
+  const uint32_t KC = (uint32_t)c.kc, Q = (uint32_t)c.q, NT = (uint32_t)c.NT, splits = r.splits;
+  if (c.family == F_K1D) return launch_k1d(ctx, c, p, splits, r.first);
   if (p.K % KC || (p.K / KC) % Q)
     return bh::fail(BH_UNSUP, std::string("conv: input channels not a whole number of ") + c.name + " trips");
-  if (c.k1r && p.K > (uint32_t)c.k1r)
-    return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " holds at most " + std::to_string(c.k1r) +
+  if (c.family == F_K1R && p.K > (uint32_t)c.kmax)
+    return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " holds at most " + std::to_string(c.kmax) +
                                   " input channels in registers");
   // k1w: a store-wave lane's 4 pixels lie in one image and its 16-B output / residual accesses are aligned
-  if (c.k1w && (p.OHW % 4 || (uintptr_t)p.c % 16 || (uintptr_t)p.res % 16))
+  if (c.family == F_K1W && (p.OHW % 4 || (uintptr_t)p.c % 16 || (uintptr_t)p.res % 16))
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " needs OH*OW % 4 == 0 and 16-B aligned output rows");
-  // k1n: a lane's gv_cx pixels lie in one image (OH*OW % gv_cx == 0) and its vector loads / stores
+  // k1n: a lane's tn pixels lie in one image (OH*OW % tn == 0) and its vector loads / stores
   // are aligned
-  const uint32_t tn = (uint32_t)c.gv_cx;
-  if (c.k1n && tn > 1 &&
+  const uint32_t tn = (uint32_t)c.tn;  // 1 but for k1n
+  if (tn > 1 &&
       (p.OHW % tn || (uintptr_t)p.b % (4u * tn) || (uintptr_t)p.c % (4u * tn) || (uintptr_t)p.res % (4u * tn)))
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " needs OH*OW % " + std::to_string(tn) +
                                   " == 0 and aligned input / output rows");
   // k1s: the bank slice [IC][OCT] and one [32][36] epilogue staging tile per wave; k1n: the bank
   // slice and the tile's biases (whole 64-float DMAs)
-  // k1w: the bank slice padded to whole 64-lane 16-B DMAs, the biases, c.k1w_sl [BM][32] staging slots per
+  // k1w: the bank slice padded to whole 64-lane 16-B DMAs, the biases, c.stage_slots [BM][32] staging slots per
   // compute wave and two counters per compute wave
-  const uint32_t nw = NT / 64 - (uint32_t)c.k1w;  // compute waves
-  const uint64_t lds = c.k1r  ? 0
-                       : c.k1w  ? (((uint64_t)p.K * c.BM / 4 + 63) / 64 * 256 + (uint64_t)((c.BM + 63) / 64) * 64 +
-                                (uint64_t)nw * c.k1w_sl * c.BM * 32 + 2 * nw) * 4
-                       : c.k1n ? ((uint64_t)p.K * c.BM + (uint64_t)((c.BM + 63) / 64) * 64) * 4
-                               : ((uint64_t)p.K * c.BM + (uint64_t)(NT / 64) * 32 * 36) * 4;
+  const uint32_t nw = NT / 64 - (uint32_t)c.store_waves;  // compute waves
+  const uint64_t lds = c.family == F_K1R   ? 0
+                       : c.family == F_K1W ? (((uint64_t)p.K * c.BM / 4 + 63) / 64 * 256 + (uint64_t)((c.BM + 63) / 64) * 64 +
+                                              (uint64_t)nw * c.stage_slots * c.BM * 32 + 2 * nw) * 4
+                       : c.family == F_K1N ? ((uint64_t)p.K * c.BM + (uint64_t)((c.BM + 63) / 64) * 64) * 4
+                                           : ((uint64_t)p.K * c.BM + (uint64_t)(NT / 64) * 32 * 36) * 4;
   if (lds > 160 * 1024) return bh::fail(BH_UNSUP, std::string("conv: bank slice too large for ") + c.name);
   const uint64_t out_bytes = (uint64_t)p.OCOHW * (p.N / p.OHW) * 4;
   if (out_bytes >= 0x7fffff00ull) return bh::fail(BH_UNSUP, "conv: output too large for the k1s kernel");
   p.c_bytes = (uint32_t)out_bytes;
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return bh::fail(BH_ERR, "conv: k1s LDS attribute");
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, c.NT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
+  if (int rc = bh::dyn_lds(k, (uint32_t)lds, "conv: k1s LDS attribute")) return rc;
+  const int occ = bh::occupancy(k, c.NT, (size_t)lds);
   const uint32_t oct = (p.M + c.BM - 1) / c.BM;
-  const uint32_t npu = (p.N + 32 * (c.k1n ? tn : 1u) - 1) / (32 * (c.k1n ? tn : 1u));
+  const uint32_t npu = (p.N + 32 * tn - 1) / (32 * tn);
   const bool full = splits >= 8;
   uint32_t bpc = splits && !full ? splits : 2;
   bpc = std::max(1u, std::min<uint32_t>(bpc, (uint32_t)std::min(occ, 4)));
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
   // blocks per OC tile: enough waves for every pixel unit, at most the CUs' share; a multiple of 8
   // rounded DOWN where that still leaves a block per XCD: rounding up put G above the resident
   // blocks (264 blocks at one block per CU: the last 8 started when the first ones ended, +50 %)
-  uint64_t per = std::max<uint64_t>(1, ((uint64_t)ncu * bpc) / oct);
+  uint64_t per = std::max<uint64_t>(1, ((uint64_t)bh::num_cus(ctx) * bpc) / oct);
   per = std::min<uint64_t>(per, (npu + nw - 1) / nw);
   per = per >= 8 ? per / 8 * 8 : 8;
   if (full) per = ((npu + nw - 1) / nw + 7) / 8 * 8;
   const uint64_t G = per * oct;
   if (G >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: k1s grid too large");
   p.tiles_m = oct;
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
-  return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, first, true, "conv_k1s", (uint32_t)lds);
+  return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, r.first, true, "conv_k1s", (uint32_t)lds);
 }
 
 }  // namespace bhk

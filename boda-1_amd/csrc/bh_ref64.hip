@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void ref64_sgemm_kernel(GemmArgs p) {
 
 std::vector<cfg_t> ref64_cfgs() {
   cfg_t c{"ref64", 1, 1, 1, 256, {}, 0};
-  c.ref64 = 1;
+  c.family = F_REF64;
   return {c};
 }
 

@@ -843,6 +843,7 @@ void reg_ring(cfg_t &c) {
 template <int TM, int TN, int BK, int D>
 cfg_t ring_conv_cfg(const char *name) {
   cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 1};
+  c.family = F_RING;
   reg_ring<TM, TN, BK, D, B_IM2COL>(c);
   reg_ring<TM, TN, BK, D, B_IMTAB>(c);
   reg_ring<TM, TN, BK, D, B_IMTAP>(c);
@@ -853,7 +854,9 @@ cfg_t ring_conv_cfg(const char *name) {
 }
 template <int TM, int TN, int BK, int D>
 cfg_t srk_conv_cfg(const char *name) {
-  cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 1, 1, (D * BK * 64 * (TM + TN) + 4) * 4};
+  cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 1};
+  c.family = F_STREAMK;
+  c.lds_bytes = (D * BK * 64 * (TM + TN) + 4) * 4;
   c.k[A_KVEC][B_IM2COL][0] = srk_kernel<TM, TN, BK, D, B_IM2COL>;
   c.k[A_KVEC][B_IMT2][0] = srk_kernel<TM, TN, BK, D, B_IMT2>;
   c.k[A_KVEC][B_IM1X1][0] = srk_kernel<TM, TN, BK, D, B_IM1X1>;
@@ -864,13 +867,16 @@ cfg_t srk_conv_cfg(const char *name) {
 }
 template <int TM, int TN, int BK, int D>
 cfg_t srk_sgemm_cfg(const char *name) {
-  cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 0, 1, (D * BK * 64 * (TM + TN) + 4) * 4};
+  cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 0};
+  c.family = F_STREAMK;
+  c.lds_bytes = (D * BK * 64 * (TM + TN) + 4) * 4;
   c.k[A_KVEC][B_KVEC][0] = srk_kernel<TM, TN, BK, D, B_KVEC>;
   return c;
 }
 template <int TM, int TN, int BK, int D>
 cfg_t ring_sgemm_cfg(const char *name) {
   cfg_t c{name, 64 * TM, 64 * TN, BK, 256, {}, 0};
+  c.family = F_RING;
   reg_ring<TM, TN, BK, D, B_KVEC>(c);
   c.k[A_KSCALAR][B_KSCALAR][0] = ring_kernel<TM, TN, BK, D, B_KSCALAR, 0>;  // (experiment: dword B, 16-B A)
   return c;
@@ -879,6 +885,7 @@ cfg_t ring_sgemm_cfg(const char *name) {
 template <int TM, int TN, int BK, int D>
 cfg_t ring_sgemm8_cfg(const char *name) {
   cfg_t c{name, 128 * TM, 64 * TN, BK, 512, {}, 0};
+  c.family = F_RING;
   c.k[A_KVEC][B_KVEC][0] = ring_kernel<TM, TN, BK, D, B_KVEC, 0, 4>;
   c.k[A_KVEC][B_KVEC][1] = ring_kernel<TM, TN, BK, D, B_KVEC, 1, 4>;
   c.k[A_KVEC][B_KVEC][2] = ring_kernel<TM, TN, BK, D, B_KVEC, 2, 4>;
@@ -973,14 +980,6 @@ size_t banks_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX, uint32_t
 
 size_t bank_offset(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX, uint32_t banks, uint32_t bank) {
   return banks_floats(OC, IC, KY, KX, banks & (bank - 1));
-}
-
-uint32_t route_bank(const cfg_t &c, uint32_t KY, uint32_t KX) {
-  if (c.dc == 4) return KY == 3 && KX == 3 ? BANK_W23 : 0;
-  if (c.dc != 5 || (uint32_t)c.dc_ky != KY || KX != KY) return 0;
-  if (KY == 5) return c.dc_s == 2 ? BANK_W25 : 0;
-  if (KY == 3) return c.dc_s == 4 ? BANK_W43 : BANK_W23;
-  return 0;
 }
 
 // the k-major bank, then the Winograd banks of the mask (cut to the kernel size's)

@@ -239,30 +239,41 @@ int launch(bh_ctx *ctx, const void *kernel, dim3 grid, dim3 block, void **args, 
 }  // namespace bh
 
 namespace {
-// the bytes a forward conv call touches, for the capture lanes: `out` is the first byte the call
-// writes (its channel slab in image 0); a slab call covers through the end of its slab in the last image
-void conv_scope(bh::op_scope &s, const float *in, const float *filts, const float *packed, uint32_t banks,
-                const float *biases, const float *res, const float *out, uint32_t out_ctot, uint32_t B, uint32_t IC,
-                uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX, uint64_t ohw) {
-  s.read(in, (uint64_t)B * IC * H * W * 4);
-  s.read(filts, (uint64_t)OC * IC * KY * KX * 4);
-  if (packed) s.read(packed, (uint64_t)bh::conv_filts_packed_floats(OC, IC, KY, KX, banks) * 4);
-  s.read(biases, (uint64_t)OC * 4);
-  s.read(res, (uint64_t)B * OC * ohw * 4);
-  s.write(out, ((uint64_t)(B - 1) * (out_ctot ? out_ctot : OC) + OC) * ohw * 4);
+// Validate the dims of a C-ABI forward conv call (tensors, eleven dims, relu, out_ctot filled in by the
+// entry) and derive the rest.
+int conv_check(bh::conv_call &cc) {
+  if (!cc.in || !cc.filts || !cc.out) return bh::fail(BH_ERR, "null tensor");
+  if (!cc.B || !cc.IC || !cc.H || !cc.W || !cc.OC || !cc.KY || !cc.KX || !cc.sy || !cc.sx)
+    return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
+  if (cc.H + 2 * cc.py < cc.KY || cc.W + 2 * cc.px < cc.KX)
+    return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
+  return BH_OK;
 }
-uint64_t conv_ohw(uint32_t H, uint32_t W, uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py,
-                  uint32_t px) {
-  return (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
+// The call writes channels [ofs, ofs + OC) of a tensor of out_ctot channels that cc.out points at.
+int conv_slab(bh::conv_call &cc, uint32_t out_ctot, uint32_t ofs) {
+  if ((uint64_t)ofs + cc.OC > out_ctot) return bh::fail(BH_ERR, "conv: output channel slab out of range");
+  cc.out_ctot = out_ctot;
+  cc.finish();
+  cc.out += (uint64_t)ofs * cc.OH * cc.OW;
+  return BH_OK;
+}
+// Open the call's op scope (roofline flops / bytes as boda_hip/ops.py's ConvShape; the bytes it touches,
+// for the capture lanes: a slab call covers through the end of its slab in the last image) and launch.
+int conv_run(bh_ctx *c, bh::conv_call &cc) {
+  cc.finish();
+  const uint64_t ohw = (uint64_t)cc.OH * cc.OW, wts = (uint64_t)cc.OC * cc.IC * cc.KY * cc.KX;
+  bh::op_scope s(c, 2.0 * cc.B * ohw * wts,
+                 4.0 * ((double)cc.B * cc.IC * cc.H * cc.W + (double)cc.B * cc.OC * ohw + (double)wts));
+  s.read(cc.in, (uint64_t)cc.B * cc.IC * cc.H * cc.W * 4);
+  s.read(cc.filts, wts * 4);
+  if (cc.packed)
+    s.read(cc.packed, (uint64_t)bh::conv_filts_packed_floats(cc.OC, cc.IC, cc.KY, cc.KX, cc.pk_banks) * 4);
+  s.read(cc.biases, (uint64_t)cc.OC * 4);
+  s.read(cc.res, (uint64_t)cc.B * cc.OC * ohw * 4);
+  s.write(cc.out, ((uint64_t)(cc.B - 1) * cc.out_ctot + cc.OC) * ohw * 4);
+  return bh::launch_conv(c, cc);
 }
 }  // namespace
-
-// roofline flops / bytes of a forward conv, as boda_hip/ops.py's ConvShape
-#define BH_CONV_SCOPE(packed_, banks_, res_, out_, ctot_)                                                        \
-  const uint64_t sc_ohw_ = conv_ohw(H, W, KY, KX, sy, sx, py, px);                                                \
-  bh::op_scope bh_op_scope_(c, 2.0 * B * sc_ohw_ * OC * IC * KY * KX,                                             \
-                            4.0 * ((double)B * IC * H * W + (double)B * OC * sc_ohw_ + (double)OC * IC * KY * KX)); \
-  conv_scope(bh_op_scope_, in, filts, packed_, banks_, biases, res_, out_, ctot_, B, IC, H, W, OC, KY, KX, sc_ohw_)
 
 extern "C" {
 
@@ -495,24 +506,18 @@ int bh_conv2d_fwd_nchw_pk(bh_ctx *c, const float *in, const float *filts, const 
                           float *out, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
                           uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu) {
   BH_ENTER_CALL(c);
-  if (!in || !filts || !out) return bh::fail(BH_ERR, "null tensor");
-  if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
-    return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
-  if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
-  BH_CONV_SCOPE(packed, BH_BANKS_ALL, nullptr, out, 0);
-  return bh::launch_conv(c, in, filts, packed, biases, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu);
+  bh::conv_call cc{in, filts, packed, BH_BANKS_ALL, biases, nullptr, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0};
+  if (int rc = conv_check(cc)) return rc;
+  return conv_run(c, cc);
 }
 
 int bh_conv2d_fwd_nchw_res(bh_ctx *c, const float *in, const float *filts, const float *packed, const float *biases,
                            const float *res, float *out, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC,
                            uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu) {
   BH_ENTER_CALL(c);
-  if (!in || !filts || !out) return bh::fail(BH_ERR, "null tensor");
-  if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
-    return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
-  if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
-  BH_CONV_SCOPE(packed, BH_BANKS_ALL, res, out, 0);
-  return bh::launch_conv(c, in, filts, packed, biases, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0, res);
+  bh::conv_call cc{in, filts, packed, BH_BANKS_ALL, biases, res, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0};
+  if (int rc = conv_check(cc)) return rc;
+  return conv_run(c, cc);
 }
 
 int bh_conv2d_fwd_nchw_slab(bh_ctx *c, const float *in, const float *filts, const float *packed,
@@ -520,15 +525,10 @@ int bh_conv2d_fwd_nchw_slab(bh_ctx *c, const float *in, const float *filts, cons
                             uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY, uint32_t KX,
                             uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu) {
   BH_ENTER_CALL(c);
-  if (!in || !filts || !out) return bh::fail(BH_ERR, "null tensor");
-  if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
-    return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
-  if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
-  if ((uint64_t)out_chan_ofs + OC > out_chans_total) return bh::fail(BH_ERR, "conv: output channel slab out of range");
-  const uint64_t ohw = (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
-  BH_CONV_SCOPE(packed, BH_BANKS_ALL, nullptr, out + out_chan_ofs * ohw, out_chans_total);
-  return bh::launch_conv(c, in, filts, packed, biases, out + out_chan_ofs * ohw, B, IC, H, W, OC, KY, KX, sy, sx,
-                         py, px, relu, out_chans_total);
+  bh::conv_call cc{in, filts, packed, BH_BANKS_ALL, biases, nullptr, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0};
+  if (int rc = conv_check(cc)) return rc;
+  if (int rc = conv_slab(cc, out_chans_total, out_chan_ofs)) return rc;
+  return conv_run(c, cc);
 }
 
 int bh_conv2d_fwd_nchw_pkb(bh_ctx *c, const float *in, const float *filts, const float *packed, uint32_t banks,
@@ -536,17 +536,11 @@ int bh_conv2d_fwd_nchw_pkb(bh_ctx *c, const float *in, const float *filts, const
                            uint32_t out_chan_ofs, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC,
                            uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu) {
   BH_ENTER_CALL(c);
-  if (!in || !filts || !out) return bh::fail(BH_ERR, "null tensor");
-  if (!B || !IC || !H || !W || !OC || !KY || !KX || !sy || !sx)
-    return bh::fail(BH_UNSUP, "conv: zero-sized dimension or stride");
-  if (H + 2 * py < KY || W + 2 * px < KX) return bh::fail(BH_UNSUP, "conv: padded input smaller than kernel");
-  if (!out_chans_total) out_chans_total = OC;
-  if ((uint64_t)out_chan_ofs + OC > out_chans_total) return bh::fail(BH_ERR, "conv: output channel slab out of range");
-  if (res && out_chans_total != OC) return bh::fail(BH_ERR, "conv: residual and channel slab together");
-  const uint64_t ohw = (uint64_t)((H + 2 * py - KY) / sy + 1) * ((W + 2 * px - KX) / sx + 1);
-  BH_CONV_SCOPE(packed, banks, res, out + out_chan_ofs * ohw, out_chans_total);
-  return bh::launch_conv(c, in, filts, packed, biases, out + out_chan_ofs * ohw, B, IC, H, W, OC, KY, KX, sy, sx, py,
-                         px, relu, out_chans_total, res, false, false, banks);
+  bh::conv_call cc{in, filts, packed, banks, biases, res, out, B, IC, H, W, OC, KY, KX, sy, sx, py, px, relu, 0};
+  if (int rc = conv_check(cc)) return rc;
+  if (int rc = conv_slab(cc, out_chans_total ? out_chans_total : OC, out_chan_ofs)) return rc;
+  if (res && cc.out_ctot != OC) return bh::fail(BH_ERR, "conv: residual and channel slab together");
+  return conv_run(c, cc);
 }
 
 int bh_conv2d_fwd_nchw(bh_ctx *c, const float *in, const float *filts, const float *biases, float *out,

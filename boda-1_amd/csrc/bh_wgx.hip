@@ -43,6 +43,7 @@
 #include "bh_gemm_dev.h"
 
 namespace bhk {
+static int launch_wgx(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 
 struct WxArgs {
   const float *u;    // 6x6: [IC4][OC32][36], positions in (group, slot) order; 4x4: bh_wino.hip's bank
@@ -818,12 +819,14 @@ cfg_t wgx_cfg(const char *name) {
   cfg_t c{name, G::OCT, XTT, XC, G::NT, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = (kern_t)(void *)wgx_kernel<MO, R, SP, NW, SK, DBG>;
   if constexpr (SK == 1) c.k[A_KVEC][B_DIRECT][1] = (kern_t)(void *)wx_combine_kernel<MO, R, NW>;
-  c.dc_wpm = SK;  // (dc == 5) 1: persistent stream-K grid, 2 / 3: whole units + a split tail
-  c.dc = 5;
-  c.dc_ky = R;
-  c.dc_kx = R;
-  c.dc_s = MO;  // output tile
-  c.dc_rin = SP;
+  c.family = F_WGX;
+  c.launch = launch_wgx;
+  c.ky = R;
+  c.kx = R;
+  c.mo = MO;
+  c.bank = R == 5 ? (MO == 2 ? BANK_W25 : 0u) : (MO == 4 ? BANK_W43 : BANK_W23);
+  c.sk = SK;
+  c.sp = SP;
   return c;
 }
 
@@ -944,15 +947,16 @@ int launch_wx_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uint3
 
 // Launch a position-split Winograd configuration: UNSUP unless a stride-1 R x R conv (R = the
 // configuration's) with pad <= R / 2, IC % 4 == 0, IC <= 64 for F(4x4,3x3) and <= 96 for F(2x2,5x5)
-// (their fp32 element error), whose strips fit the configuration's slot. u: the bank of the configuration's
-// form (6x6: wx_pack; 4x4: bh_wino.hip's). One block per unit (whole units), or (dc_wpm) a resident
+// (their fp32 element error), whose strips fit the configuration's slot. r.bank: the bank of the configuration's
+// form (6x6: wx_pack; 4x4: bh_wino.hip's). One block per unit (whole units), or (cfg_t::sk) a resident
 // stream-K grid over the (unit, stage) iterations.
-int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, const float *bias, const float *res,
-               float *out, uint32_t out_ctot, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
-               uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu, int wt, uint32_t splits,
-               bool first) {
-  const uint32_t R = (uint32_t)c.dc_ky, MO = (uint32_t)c.dc_s, N = MO + R - 1;
-  if (KY != R || KX != R || sy != 1 || sx != 1 || py != px || py > R / 2)
+static int launch_wgx(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &, const route_t &r) {
+  if (!r.bank) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for other kernel sizes");
+  const uint32_t B = cc.B, IC = cc.IC, H = cc.H, W = cc.W, OC = cc.OC, py = cc.py, px = cc.px, out_ctot = cc.out_ctot;
+  const float *const res = cc.res;
+  float *const out = cc.out;
+  const uint32_t R = (uint32_t)c.ky, MO = (uint32_t)c.mo, N = MO + R - 1;
+  if (cc.KY != R || cc.KX != R || cc.sy != 1 || cc.sx != 1 || py != px || py > R / 2)
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for stride-1 square-padded convs of its kernel size");
   if (IC % XC) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " needs IC % 4 == 0");
   // the 6x6 forms' element error grows as sqrt(IC) (the transformed-domain sum dominates it): measured
@@ -979,7 +983,7 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
     const uint32_t a = gi * XTT, b = std::min(T, a + XTT) - 1;
     rin = std::max(rin, vrow(b) + N - vrow(a));
   }
-  const uint32_t SP = (uint32_t)c.dc_rin, XNT = (uint32_t)c.NT;
+  const uint32_t SP = (uint32_t)c.sp, XNT = (uint32_t)c.NT;
   if ((uint64_t)XC * rin * WPM > (uint64_t)SP * XNT)
     return bh::fail(BH_UNSUP, std::string("conv: input strip too large for ") + c.name);
   // (smaller strips than a configuration's slot are left to the configurations with fewer DMAs)
@@ -990,24 +994,24 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
   const uint64_t ubytes = (uint64_t)((IC + 3) & ~3u) * OC32 * P * 4;
   if (ubytes >= 0x7fffff00ull) return bh::fail(BH_UNSUP, "conv: Winograd bank too large");
   WxArgs p{};
-  p.u = u; p.in = in; p.out = out; p.bias = bias; p.res = res;
+  p.u = r.bank; p.in = cc.in; p.out = out; p.bias = cc.biases; p.res = res;
   p.u_bytes = (uint32_t)ubytes;
   p.in_bytes = (uint32_t)((uint64_t)B * IC * H * W * 4);
   p.out_bytes = (uint32_t)out_bytes;
   p.OC = OC; p.OC32 = OC32; p.IC = IC; p.B = B; p.H = H; p.W = W; p.pad = pad;
   p.OH = OH; p.OW = OW; p.OHW = OH * OW; p.HW = H * W; p.ICHW = IC * H * W; p.OCOHW = out_ctot * OH * OW;
   p.TW = TW; p.TPI = TPI; p.VH = VH; p.T = T; p.WPM = WPM; p.RW = rin * WPM;
-  bh::fastdiv f = bh::make_fastdiv(TW); p.tw_m = f.m; p.tw_s = f.s;
-  f = bh::make_fastdiv(TPI); p.tpi_m = f.m; p.tpi_s = f.s;
-  f = bh::make_fastdiv(VH); p.vh_m = f.m; p.vh_s = f.s;
-  f = bh::make_fastdiv(WPM); p.wpm_m = f.m; p.wpm_s = f.s;
-  f = bh::make_fastdiv(p.RW); p.rw_m = f.m; p.rw_s = f.s;
+  bh::set_fd(TW, p.tw_m, p.tw_s);
+  bh::set_fd(TPI, p.tpi_m, p.tpi_s);
+  bh::set_fd(VH, p.vh_m, p.vh_s);
+  bh::set_fd(WPM, p.wpm_m, p.wpm_s);
+  bh::set_fd(p.RW, p.rw_m, p.rw_s);
   p.ngr = ngroups;
-  f = bh::make_fastdiv(ngroups); p.ngr_m = f.m; p.ngr_s = f.s;
+  bh::set_fd(ngroups, p.ngr_m, p.ngr_s);
   p.ipt = IC / XC;
-  f = bh::make_fastdiv(p.ipt); p.ipt_m = f.m; p.ipt_s = f.s;
-  p.relu = relu;
-  p.wt = wt;
+  bh::set_fd(p.ipt, p.ipt_m, p.ipt_s);
+  p.relu = cc.relu;
+  p.wt = r.wt;
   p.vst = (OW % MO == 0 && ((uintptr_t)out % (4 * MO)) == 0 && ((uintptr_t)res % (4 * MO)) == 0) ? 1 : 0;
   const uint32_t OCT = (uint32_t)c.BM, octiles = (OC + OCT - 1) / OCT;
   const uint64_t units = (uint64_t)ngroups * octiles;
@@ -1018,16 +1022,13 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
   const uint32_t lds = (std::max(2 * SP * XNT + 2 * NPG * XC * XTT * PS, XNT * XS) + 4) * 4;
   if (lds > 160 * 1024) return bh::fail(BH_UNSUP, std::string("conv: LDS too small for ") + c.name);
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return bh::fail(BH_ERR, "conv: Winograd LDS attribute");
+  if (int rc = bh::dyn_lds(k, lds, "conv: Winograd LDS attribute")) return rc;
   uint32_t G = (uint32_t)units;
-  if (c.dc_wpm == 3) {
+  // blocks resident at once (the split forms' rounds)
+  const uint64_t C = c.sk ? (uint64_t)bh::num_cus(ctx) * (uint32_t)std::min(bh::occupancy(k, (int)XNT, (size_t)lds), 2) : 0;
+  if (c.sk == 3) {
     // whole units in full rounds of the resident blocks; the tail round's T units as NOG pieces each,
     // when they fit one round
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, (int)XNT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
-    const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-    const uint64_t C = (uint64_t)ncu * (uint32_t)std::min(occ, 2);
     const uint32_t NOG = XNT / 64 / NPG;
     const uint64_t R = units / C, T = units - R * C;
     p.ipb = (uint32_t)units;
@@ -1037,12 +1038,8 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
       p.total_it = NOG;
       G = (uint32_t)(R * C + T * NOG);
     }
-  } else if (c.dc_wpm == 2) {
+  } else if (c.sk == 2) {
     // whole units in full rounds of the resident blocks; the tail round's T units in S pieces each
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, (int)XNT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
-    const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-    const uint64_t C = (uint64_t)ncu * (uint32_t)std::min(occ, 2);
     const uint64_t R = units / C, T = units - R * C;
     const uint32_t S = T ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(p.ipt, C / T)) : 1u;
     if (S == 1) {
@@ -1059,16 +1056,11 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
       p.ws = ws_of(ctx);
       p.cnt = cnt_of(ctx);
     }
-  } else if (c.dc_wpm) {
+  } else if (c.sk) {
     // stream-K: as many blocks as are resident at once, the (unit, stage) iterations dealt equally
-    
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, (int)XNT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
-    const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     const uint64_t total = units * p.ipt;
     if (total >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: too many Winograd iterations");
-    const uint64_t g = (uint64_t)ncu * (uint32_t)std::min(occ, 2);
-    p.ipb = (uint32_t)((total + g - 1) / g);
+    p.ipb = (uint32_t)((total + C - 1) / C);
     G = (uint32_t)((total + p.ipb - 1) / p.ipb);
     p.total_it = (uint32_t)total;
     const size_t slab = (size_t)(16 / (XNT / ((XNT / 64 / NPG) * 64))) * XNT * MO * MO;  // NR * NT * MO^2 floats
@@ -1078,14 +1070,12 @@ int launch_wgx(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, con
     p.ws = ws_of(ctx);
     p.cnt = cnt_of(ctx);
   }
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
   // splits 20 on a stream-K configuration: the cut units summed by wx_combine_kernel (a second launch)
-  p.sepc = (c.dc_wpm == 1 && splits == 20) ? 1 : 0;
-  if (!p.sepc) return bh::launch(ctx, k, dim3(G, 1, 1), dim3(XNT), args, first, true, "conv_wgx", lds);
-  int rc = bh::launch(ctx, k, dim3(G, 1, 1), dim3(XNT), args, first, false, "conv_wgx", lds);
+  p.sepc = (c.sk == 1 && r.splits == 20) ? 1 : 0;
+  if (!p.sepc) return bh::launch(ctx, k, dim3(G, 1, 1), dim3(XNT), args, r.first, true, "conv_wgx", lds);
+  int rc = bh::launch(ctx, k, dim3(G, 1, 1), dim3(XNT), args, r.first, false, "conv_wgx", lds);
   if (rc != BH_OK) return rc;
   const uint32_t NR = 16 / (XNT / ((XNT / 64 / NPG) * 64));
   return bh::launch(ctx, (const void *)c.k[A_KVEC][B_DIRECT][1], dim3((uint32_t)units * NR, 1, 1), dim3(XNT), args,

@@ -40,6 +40,7 @@
 #include "bh_gemm_dev.h"
 
 namespace bhk {
+static int launch_wg(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 
 struct WgArgs {
   const float *u;    // Winograd bank [IC4][OC32][16] (rotated chunks)
@@ -947,12 +948,14 @@ cfg_t wgp_cfg(const char *name) {
   cfg_t c{name, 32 * NWO, 32 * NWT, WCI, 64 * NWO * NWT, {}, 1};
   c.k[A_KVEC][B_DIRECT][0] = (kern_t)(void *)wgp_kernel<NWO, NWT, D, V4, SP, IL, DBG>;
   c.k[A_KVEC][B_DIRECT][1] = (kern_t)(void *)wg_combine_kernel<NWO, NWT>;
-  c.dc = 4;
-  c.dc_ky = 3;
-  c.dc_kx = 3;
-  c.dc_s = V4;
-  c.dc_rin = SP;
-  c.dc_ci = D;
+  c.family = F_WINO;
+  c.launch = launch_wg;
+  c.ky = 3;
+  c.kx = 3;
+  c.bank = BANK_W23;
+  c.v4 = V4;
+  c.sp = SP;
+  c.slots = D;
   return c;
 }
 
@@ -1001,19 +1004,22 @@ int launch_wino_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uin
 // equally; 5..8: blocks per CU 1..4, whole tiles per block; + 10: OC tiles slowest; + 20: the
 // stream-K modes' cut tiles summed by wg_combine_kernel (a second launch) instead of their last
 // arrivers.
-int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, const float *bias, const float *res,
-              float *out, uint32_t out_ctot, uint32_t B, uint32_t IC, uint32_t H, uint32_t W, uint32_t OC, uint32_t KY,
-              uint32_t KX, uint32_t sy, uint32_t sx, uint32_t py, uint32_t px, int relu, int wt, uint32_t splits,
-              bool first) {
-  if (KY != 3 || KX != 3 || sy != 1 || sx != 1 || py > 1 || px > 1)
+static int launch_wg(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &, const route_t &r) {
+  if (!r.bank) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for 3x3 convs");
+  const uint32_t B = cc.B, IC = cc.IC, H = cc.H, W = cc.W, OC = cc.OC, py = cc.py, px = cc.px, out_ctot = cc.out_ctot;
+  const float *const res = cc.res;
+  float *const out = cc.out;
+  uint32_t splits = r.splits;
+  const bool first = r.first;
+  if (cc.KY != 3 || cc.KX != 3 || cc.sy != 1 || cc.sx != 1 || py > 1 || px > 1)
     return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for stride-1 3x3 convs with pad <= 1");
   if (IC % WCI) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " needs IC % 4 == 0");
-  if (c.dc_s && W % 4) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for W % 4 == 0 (no row masks)");
+  if (c.v4 && W % 4) return bh::fail(BH_UNSUP, std::string("conv: ") + c.name + " is for W % 4 == 0 (no row masks)");
   WgArgs p{};
   const uint32_t OH = H + 2 * py - 2, OW = W + 2 * px - 2;
   const uint32_t TH = (OH + 1) / 2, TW = (OW + 1) / 2, TPI = TH * TW;
   const uint64_t T64 = (uint64_t)B * TPI;
-  const uint32_t OCT = (uint32_t)c.BM, TT = (uint32_t)c.BN, NT = (uint32_t)c.NT, D = (uint32_t)c.dc_ci;
+  const uint32_t OCT = (uint32_t)c.BM, TT = (uint32_t)c.BN, NT = (uint32_t)c.NT, D = (uint32_t)c.slots;
   const uint32_t VH = std::max(H + 2 * py, 2 * TH + 2);
   const uint32_t WPM = (std::max(W + 1, 2 * TW + 2 - px) + 3) & ~3u;
   if (T64 >= (1u << 30) || (uint64_t)B * VH >= (1u << 30)) return bh::fail(BH_UNSUP, "conv: too many Winograd tiles");
@@ -1024,33 +1030,33 @@ int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, cons
     const uint32_t a = gi * TT, b = std::min(T, a + TT) - 1;
     rin = std::max(rin, vrow(b) + 4 - vrow(a));
   }
-  const uint32_t PW = 4, SP = (uint32_t)c.dc_rin;  // 16-B strip pieces
+  const uint32_t PW = 4, SP = (uint32_t)c.sp;  // 16-B strip pieces
   if ((uint64_t)WCI * rin * WPM > (uint64_t)SP * NT * PW)
     return bh::fail(BH_UNSUP, std::string("conv: input strip too large for ") + c.name);
   const uint64_t out_bytes = (uint64_t)B * out_ctot * OH * OW * 4;
   if (out_bytes >= 0x7fffff00ull) return bh::fail(BH_UNSUP, "conv: output too large for the Winograd kernel");
   const uint32_t OC32 = (OC + 31) & ~31u;
-  p.u = u; p.in = in; p.out = out; p.bias = bias; p.res = res;
+  p.u = r.bank; p.in = cc.in; p.out = out; p.bias = cc.biases; p.res = res;
   p.u_bytes = (uint32_t)(wino_bank_floats(OC, IC) * 4);
   p.in_bytes = (uint32_t)((uint64_t)B * IC * H * W * 4);
   p.out_bytes = (uint32_t)out_bytes;
   p.OC = OC; p.OC32 = OC32; p.IC = IC; p.B = B; p.H = H; p.W = W; p.py = py; p.px = px;
   p.OH = OH; p.OW = OW; p.OHW = OH * OW; p.HW = H * W; p.ICHW = IC * H * W; p.OCOHW = out_ctot * OH * OW;
   p.TW = TW; p.TPI = TPI; p.VH = VH; p.T = T; p.WPM = WPM; p.RW = rin * WPM;
-  bh::fastdiv f = bh::make_fastdiv(TW); p.tw_m = f.m; p.tw_s = f.s;
-  f = bh::make_fastdiv(TPI); p.tpi_m = f.m; p.tpi_s = f.s;
-  f = bh::make_fastdiv(VH); p.vh_m = f.m; p.vh_s = f.s;
-  f = bh::make_fastdiv(WPM); p.wpm_m = f.m; p.wpm_s = f.s;
-  f = bh::make_fastdiv(p.RW); p.rw_m = f.m; p.rw_s = f.s;
+  bh::set_fd(TW, p.tw_m, p.tw_s);
+  bh::set_fd(TPI, p.tpi_m, p.tpi_s);
+  bh::set_fd(VH, p.vh_m, p.vh_s);
+  bh::set_fd(WPM, p.wpm_m, p.wpm_s);
+  bh::set_fd(p.RW, p.rw_m, p.rw_s);
   const uint32_t octiles = (OC + OCT - 1) / OCT, ipt = IC / WCI;
   const uint64_t ntile = (uint64_t)ngroups * octiles, total = ntile * ipt;
   if (total >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: too many iterations");
   p.tiles_m = octiles;
-  f = bh::make_fastdiv(octiles); p.tm_m = f.m; p.tm_s = f.s;
+  bh::set_fd(octiles, p.tm_m, p.tm_s);
   p.ipt = ipt;
-  f = bh::make_fastdiv(ipt); p.ipt_m = f.m; p.ipt_s = f.s;
-  p.relu = relu;
-  p.wt = wt;
+  bh::set_fd(ipt, p.ipt_m, p.ipt_s);
+  p.relu = cc.relu;
+  p.wt = r.wt;
   // 8-B stores need an 8-B aligned output (and residual): callers may pass any float offset
   p.ow2 = (OW % 2 == 0 && ((uintptr_t)out & 7) == 0 && ((uintptr_t)res & 7) == 0) ? 1 : 0;
   // dynamic LDS: D strip slots (guard + strip), three V buffers, the ticket flag
@@ -1058,10 +1064,8 @@ int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, cons
   const uint32_t lds = (D * slot + 3 * WCI * TT * 16 + 4) * 4;
   if (lds > 160 * 1024) return bh::fail(BH_UNSUP, std::string("conv: LDS too small for ") + c.name);
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return bh::fail(BH_ERR, "conv: Winograd LDS attribute");
-  int occ = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, (int)NT, (size_t)lds) != hipSuccess || occ < 1) occ = 1;
+  if (int rc = bh::dyn_lds(k, lds, "conv: Winograd LDS attribute")) return rc;
+  const int occ = bh::occupancy(k, (int)NT, (size_t)lds);
   // splits: + 20 = cut tiles summed by wg_combine_kernel after the grid (stream-K modes); + 10 = OC
   // tile slowest
   p.sepc = splits >= 20 ? 1 : 0;
@@ -1069,12 +1073,11 @@ int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, cons
   p.ocs = splits >= 10 ? 1 : 0;
   if (splits >= 10) splits -= 10;
   p.ngr = ngroups;
-  f = bh::make_fastdiv(ngroups); p.ngr_m = f.m; p.ngr_s = f.s;
+  bh::set_fd(ngroups, p.ngr_m, p.ngr_s);
   const bool whole = splits > 4;
   uint32_t bpc = splits ? (whole ? splits - 4 : splits) : 1;
   bpc = std::max(1u, std::min<uint32_t>(bpc, (uint32_t)std::min(occ, 4)));
-  const uint32_t ncu = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  uint64_t G = (uint64_t)ncu * bpc;
+  uint64_t G = (uint64_t)bh::num_cus(ctx) * bpc;
   uint32_t ipb = (uint32_t)((total + G - 1) / G);
   if (whole) ipb = (uint32_t)((ntile + G - 1) / G) * ipt;
   G = (total + ipb - 1) / ipb;
@@ -1085,9 +1088,7 @@ int launch_wg(bh_ctx *ctx, const cfg_t &c, const float *u, const float *in, cons
   if (rc != BH_OK) return rc;
   p.ws = ws_of(ctx);
   p.cnt = cnt_of(ctx);
-#ifdef BH_KTRACE
-  p.trace = (unsigned long long *)ctx->stamps + 65536;
-#endif
+  bh::set_trace(ctx, p);
   void *args[] = {&p};
   if (whole) p.sepc = 0;  // no cut tiles
   if (!p.sepc) return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(NT), args, first, true, "conv_wino", lds);
