@@ -264,13 +264,6 @@ const char *const BCKI_NAMES[] = {"32x128", "32x256", "ref64"};
 const char *const BCKF_NAMES[] = {"32x32", "64x64", "ref64"};
 constexpr int NBCK = 3, BCK_REF64 = 2;
 
-bool fits(uint64_t bytes) { return bytes < (uint64_t)OOB - 64; }
-void fd(uint32_t d, uint32_t &m, uint32_t &s) {
-  bh::fastdiv f = bh::make_fastdiv(d ? d : 1);
-  m = f.m;
-  s = f.s;
-}
-
 struct bck_dims {
   uint32_t B, IC, H, W, OC, KY, KX, sy, sx, py, px, OH, OW;
   explicit bck_dims(const uint32_t *d)
@@ -300,7 +293,7 @@ uint32_t bckf_splits(bh_ctx *ctx, const bck_dims &s, int cfg, uint32_t &cps) {
   const uint32_t bm = cfg ? 64 : 32;
   const uint64_t Q = (uint64_t)s.IC * s.KY * s.KX, R = (uint64_t)s.B * s.OH * s.OW;
   const uint64_t tiles = ((s.OC + bm - 1) / bm) * ((Q + bm - 1) / bm);
-  const uint32_t nch = (uint32_t)((R + 63) / 64), ncu = ctx ? (uint32_t)ctx->prop.multiProcessorCount : 256u;
+  const uint32_t nch = (uint32_t)((R + 63) / 64), ncu = ctx ? bh::num_cus(ctx) : 256u;
   uint32_t S = ctx && ctx->bck_splits[1] > 0 ? (uint32_t)ctx->bck_splits[1]
                                              : (uint32_t)std::min<uint64_t>((2ull * ncu + tiles - 1) / tiles, 64);
   if (!(ctx && ctx->bck_splits[1] > 0)) S = std::min(S, std::max(1u, nch / 2));
@@ -326,9 +319,10 @@ int launch_filts(bh_ctx *ctx, BckArgs &p, const bck_dims &s, bool last) {
   p.ocp = tm * bm;
   p.qp = tn * bm;
   if (tm > 65535 || p.S > 65535) return bh::fail(BH_UNSUP, "bck conv: filter-gradient grid too large");
-  int rc = ensure_ws(ctx, (size_t)p.S * p.ocp * p.qp * 4);
+  bh::scratch_t sc;
+  int rc = bh::scratch(ctx, (size_t)p.S * p.ocp * p.qp * 4, 0, sc);
   if (rc != BH_OK) return rc;
-  p.ws = ws_of(ctx);
+  p.ws = sc.ws;
   const void *k = cfg ? (const void *)bckf_kernel<64, 64> : (const void *)bckf_kernel<32, 32>;
   rc = bh::launch(ctx, k, dim3(tn, tm, p.S), dim3(cfg ? 256 : 64), args, true, false, "bck_filts");
   if (rc != BH_OK) return rc;
@@ -379,7 +373,7 @@ size_t bck_filts_packed_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t K
 int launch_bck_filts_pack(bh_ctx *ctx, const float *filts, float *packed, uint32_t OC, uint32_t IC, uint32_t KY,
                           uint32_t KX, bool first, bool last) {
   const uint64_t n = (uint64_t)OC * IC * KY * KX;
-  if (!fits(n * 4)) return fail(BH_UNSUP, "bck conv: filter bank larger than 2 GiB");
+  if (!fits_buffer(n * 4)) return fail(BH_UNSUP, "bck conv: filter bank larger than 2 GiB");
   float *wt = packed ? packed : (float *)ctx->bckw;
   void *args[] = {&filts, &wt, &OC, &IC, &KY, &KX};
   int rc = launch(ctx, (const void *)xflip_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), args, first,
@@ -393,7 +387,7 @@ int launch_bck(bh_ctx *ctx, const float *in, const float *filts, const float *pa
   const bck_dims s(d);
   const uint64_t in_b = (uint64_t)s.B * s.IC * s.H * s.W * 4, og_b = (uint64_t)s.B * s.OC * s.OH * s.OW * 4;
   const uint64_t f_b = (uint64_t)s.OC * s.IC * s.KY * s.KX * 4;
-  if (!fits(in_b) || !fits(og_b) || !fits(f_b))
+  if (!fits_buffer(in_b) || !fits_buffer(og_b) || !fits_buffer(f_b))
     return fail(BH_UNSUP, "bck conv: a tensor of 2 GiB or more cannot be addressed through a buffer resource");
   if ((uint64_t)s.B * s.OH * s.OW >= (1u << 31) - 64) return fail(BH_UNSUP, "bck conv: reduction extent too large");
   BckArgs p{};
@@ -403,10 +397,10 @@ int launch_bck(bh_ctx *ctx, const float *in, const float *filts, const float *pa
   p.sy = s.sy; p.sx = s.sx; p.py = s.py; p.px = s.px; p.OH = s.OH; p.OW = s.OW;
   p.OHW = s.OH * s.OW; p.HW = s.H * s.W; p.KYX = s.KY * s.KX; p.Q = s.IC * p.KYX; p.R = s.B * p.OHW;
   p.in_bytes = (uint32_t)in_b; p.ogl_bytes = (uint32_t)og_b; p.filts_bytes = (uint32_t)f_b;
-  fd(p.OHW, p.ohw_m, p.ohw_s);
-  fd(p.OW, p.ow_m, p.ow_s);
-  fd(p.KYX, p.kyx_m, p.kyx_s);
-  fd(p.KX, p.kx_m, p.kx_s);
+  set_fd(p.OHW, p.ohw_m, p.ohw_s);
+  set_fd(p.OW, p.ow_m, p.ow_s);
+  set_fd(p.KYX, p.kyx_m, p.kyx_s);
+  set_fd(p.KX, p.kx_m, p.kx_s);
   // the input gradient goes last: the forward route's final dispatch records the call's stop event
   int rc = BH_OK;
   if (biases_grad) rc = launch_bias(ctx, p, ctx->bck_cfg[1] == BCK_REF64, !filts_grad && !in_grad);

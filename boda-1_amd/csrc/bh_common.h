@@ -15,8 +15,9 @@
 namespace bh {
 struct op_scope;
 }
-// Capture-time lane scheduler (bh_runtime.hip, DESIGN.md "Capture lanes"). Lane 0 is the context's own
-// stream with the context's own scratch; lanes 1.. are side streams, each with split-K scratch of its own.
+// Capture-time lane scheduler (bh_runtime.hip, DESIGN.md "Capture lanes"). Lane 0 is the context's lane:
+// its stream is bh_ctx::stream and every eager call runs on it; lanes 1.. are the side streams of a
+// capture. Each lane has split-K scratch of its own, handed out by bh::scratch alone.
 struct bh_lane {
   hipStream_t stream = nullptr;
   void *ws = nullptr;  // split-K workspace of ops on this lane
@@ -29,7 +30,7 @@ struct bh_sched {
   int lanes = 1;            // BH_CAPTURE_LANES (1: one chain of dependent launches)
   double narrow_us = 0;     // BH_CAPTURE_NARROW_US: ops with a roofline time below this are spread
   bool capturing = false;   // between bh_capture_begin and bh_capture_end
-  bh_lane lane[bh_lanes::MAX_LANES];  // [0]: stream / scratch unused (the context's own)
+  bh_lane lane[bh_lanes::MAX_LANES];
   std::vector<hipEvent_t> ev;         // timing-disabled events of the forks, joins and cross-lane edges
   size_t ev_used = 0;
   bh_lanes::tracker trk;
@@ -43,12 +44,10 @@ struct bh_sched {
 
 struct bh_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // sched.lane[0].stream (bh_init)
   hipDeviceProp_t prop{};
   std::vector<hipEvent_t> events;  // pool; ids index into it
   int events_used = 0;
-  void *ws = nullptr;  // split-K workspace, grown on demand
-  size_t ws_bytes = 0;
   int ovr_cfg[2] = {-1, -1};  // tuning override per op (0 sgemm, 1 conv); -1 = table/heuristic
   uint32_t ovr_splits[2] = {0, 0};
   int ovr_red[2] = {0, 0};
@@ -58,8 +57,6 @@ struct bh_ctx {
   hipEvent_t t_start = nullptr;        // bh_time_next_call: events for the next call's
   hipEvent_t t_stop = nullptr;         //   first / last kernel dispatch
   double stamp_hz = 100e6;
-  void *cnt = nullptr;  // split-K arrival tickets
-  uint64_t cnt_n = 0;
   void *wpack = nullptr;  // k-major filter bank for the ring conv kernels, grown on demand
   size_t wpack_bytes = 0;
   // backward conv (bh_bck.hip): overrides of op 2 (input gradient) / op 3 (filter gradient), and the
@@ -111,10 +108,19 @@ struct op_scope {
 };
 int lane_resolve(bh_ctx *ctx, size_t ws_need);  // pick the open scope's lane (no-op outside a capture)
 int barrier(bh_ctx *ctx);                       // join every lane into the context's stream
-// scratch of the lane the open scope runs on (the context's own on lane 0 / outside a scope)
-int lane_ws(bh_ctx *ctx, size_t bytes);
-int lane_cnt(bh_ctx *ctx, uint64_t n);
-int lane_wpack(bh_ctx *ctx, size_t bytes);
+// Split-K / stream-K scratch of a call: ws_bytes of workspace and `tickets` zeroed arrival tickets (each
+// tile's last arriver resets its own); 0 = not needed, that pointer stays null. Picks the open scope's lane
+// (with the workspace need: a narrow op that needs more than a side lane holds runs on lane 0) and hands out
+// that lane's buffers; outside a scope, lane 0's. Lane 0 grows on demand, a side lane only in
+// bh_capture_begin; nothing grows inside a capture (BH_ERR: run the op once eagerly first).
+struct scratch_t {
+  float *ws = nullptr;
+  uint32_t *cnt = nullptr;
+};
+int scratch(bh_ctx *ctx, size_t ws_bytes, uint64_t tickets, scratch_t &out);
+// The context's one filter-bank pack buffer, grown to `bytes`. Inside a capture the open scope writes then
+// reads it, so it is ordered against every other op that repacks and runs on lane 0.
+int pack_buffer(bh_ctx *ctx, size_t bytes, float *&out);
 
 // Magic-number unsigned division for 0 <= n < 2^31, 1 <= d < 2^31:
 // q = (umulhi(n, m) + n) >> s.
@@ -199,11 +205,12 @@ struct call_scope : device_scope {
     c->t_stop = nullptr;
   }
 };
-// Grow a per-context device buffer to at least `want` bytes (+25 % headroom). Refuses to
+// Grow a per-context device buffer to at least `want` bytes (+25 % with headroom). Refuses to
 // allocate while the context's stream is capturing (a capture records no allocation: run the
 // op once eagerly first). The outgrown buffer is kept until the context is destroyed when a
 // captured graph may still reference it, freed otherwise.
-int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, const char *what);
+int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, const char *what,
+                bool headroom = true);
 }  // namespace bh
 
 #define BH_ENTER(c)  \

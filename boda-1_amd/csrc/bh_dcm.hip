@@ -33,13 +33,6 @@ namespace bhk {
 static int launch_dcm(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmArgs &p, const route_t &r);
 namespace {
 
-// logical block of hardware block bid: blocks b, b+8, ... share an XCD under round-robin
-// placement, so give each XCD a contiguous run of iterations (its L2 sees neighbouring tiles)
-__device__ __forceinline__ uint32_t dcm_lb(uint32_t bid, uint32_t G) {
-  const uint32_t xcd = bid & 7, q = G >> 3, r = G & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // Strip: [CI][RIN][WPM], WPM >= W + px; columns W .. WPM-1 of every row stay zero (misses), so a
 // tap left of the image wraps into the previous row's zero tail (a zero guard precedes the strip
 // for its first row) and a tap right of it reads this row's tail: no per-step select. V4: rows in
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(256 * WO) void dcm_kernel(GemmArgs p) {
   const int wp = wave & 3, wo = wave >> 2;  // pixel group, output-channel group
   KT(0);
 
-  const uint32_t lb = dcm_lb(blockIdx.x, gridDim.x);
+  const uint32_t lb = xcd_contig(blockIdx.x, gridDim.x);
   const uint32_t it0 = lb * p.ipb, it1 = min(p.total_it, it0 + p.ipb);
   const uint32_t Hp = p.H + 2 * p.py;
   // the strip guards stay zero (no DMA targets them); the first stage's barrier orders these
@@ -517,30 +510,23 @@ static int launch_dcm(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, Gemm
   const uint64_t ntile = (uint64_t)ptiles * octiles, total = ntile * ipt;
   if (total >= (1u << 31)) return bh::fail(BH_UNSUP, "conv: too many iterations");
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
-  const int occ = bh::occupancy(k, c.NT);
-  const bool whole = splits > 4;
-  uint32_t bpc = splits ? (whole ? splits - 4 : splits) : 2;
-  bpc = std::max(1u, std::min<uint32_t>(bpc, (uint32_t)std::min(occ, 4)));
-  uint64_t G = (uint64_t)bh::num_cus(ctx) * bpc;
-  uint32_t ipb = (uint32_t)((total + G - 1) / G);
-  if (whole) ipb = (uint32_t)((ntile + G - 1) / G) * ipt;
-  G = (total + ipb - 1) / ipb;
+  const uint32_t max_bpc = (uint32_t)std::min(bh::occupancy(k, c.NT), 4);
+  const bh::sk_grid g = bh::plan_sk_grid(ntile, ipt, bh::num_cus(ctx), splits, 2, max_bpc);
   p.ipt = ipt;
-  p.ipb = ipb;
+  p.ipb = g.ipb;
   p.total_it = (uint32_t)total;
   p.tiles_m = octiles;
   p.tiles_n = cc.B;  // images (strip rows past the last image miss)
   bh::set_fd(ipt, p.ipt_m, p.ipt_s);
   bh::set_fd(octiles, p.tm_m, p.tm_s);
   bh::set_fd(Hp, p.kyx_m, p.kyx_s);
-  int rc = ensure_ws(ctx, (size_t)2 * G * c.BM * c.BN * 4);  // two tile slabs per block
-  if (rc == BH_OK) rc = ensure_cnt(ctx, (size_t)ntile);
-  if (rc != BH_OK) return rc;
-  p.ws = ws_of(ctx);
-  p.cnt = cnt_of(ctx);
+  bh::scratch_t sc;
+  if (int rc = bh::scratch(ctx, (size_t)2 * g.G * c.BM * c.BN * 4, ntile, sc)) return rc;  // two tile slabs per block
+  p.ws = sc.ws;
+  p.cnt = sc.cnt;
   bh::set_trace(ctx, p);
   void *args[] = {&p};
-  return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, r.first, true, "conv_direct_mc");
+  return bh::launch(ctx, k, dim3((uint32_t)g.G, 1, 1), dim3(c.NT), args, r.first, true, "conv_direct_mc");
 }
 
 }  // namespace bhk

@@ -808,21 +808,7 @@ int cfg_index(int op, std::string const &name) {
   return -1;
 }
 
-bool fits_buffer(uint64_t bytes) { return bytes < (uint64_t)OOB - 64; }
-
 using bh::set_fd;
-
-}  // namespace
-
-namespace bhk {
-// (of the lane the call runs on: bh_runtime.hip, capture lanes)
-int ensure_ws(bh_ctx *ctx, size_t bytes) { return bh::lane_ws(ctx, bytes); }
-
-// split-K arrival tickets: zeroed at allocation, reset by each tile's last arriver
-int ensure_cnt(bh_ctx *ctx, uint64_t n) { return bh::lane_cnt(ctx, n); }
-}  // namespace bhk
-
-namespace {
 
 // Number of K splits: enough blocks to cover the CUs twice, at least MIN_KT K tiles per split.
 uint32_t plan_splits(uint32_t tiles, uint32_t K, int BK, uint32_t ncu) {
@@ -952,6 +938,7 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
   const uint64_t nblk = (uint64_t)p.tiles_m * p.tiles_n;
   if (nblk > 0x7fffffffu) return bh::fail(BH_UNSUP, std::string(what) + ": grid too large");
   const uint32_t ncu = bh::num_cus(ctx);
+  bh::scratch_t sc;
   p.tbm = c.BM;
   p.tbn = c.BN;
   if (bld == B_IMTAB && !c.k[ald][bld][0]) bld = B_IM2COL;  // table / one-tap loaders: ring kernels only
@@ -970,44 +957,32 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
     S = (p.K + p.ks - 1) / p.ks;
     void *args[] = {&p};
     if (S > 1) {
-      int rc = ensure_ws(ctx, (size_t)S * nblk * c.BM * c.BN * 4);
-      if (rc == BH_OK) rc = ensure_cnt(ctx, nblk);
-      if (rc != BH_OK) return rc;
-      p.ws = ws_of(ctx);
-      p.cnt = cnt_of(ctx);
+      if (int rc = bh::scratch(ctx, (size_t)S * nblk * c.BM * c.BN * 4, nblk, sc)) return rc;
+      p.ws = sc.ws;
+      p.cnt = sc.cnt;
     }
     return bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, true, what);
   }
   if (c.family == F_STREAMK) {
-    // persistent stream-K grid (srk_kernel): ncu x blocks-per-CU blocks share the op's
-    // (tile, K tile) iterations equally; ch.splits overrides blocks per CU
+    // persistent stream-K grid (srk_kernel): ncu x blocks-per-CU blocks share the op's (tile, K tile)
+    // iterations; ch.splits picks blocks per CU and equal deals or whole tiles (bh_skgrid.h), by
+    // default as many blocks per CU as the LDS holds, two at most
     kern_t k = c.k[ald][bld][0];
     if (!k) return bh::fail(BH_ERR, std::string(what) + ": loader combination not instantiated");
     const uint32_t ipt = (p.K + c.BK - 1) / c.BK;
-    const uint64_t total = nblk * ipt;
-    if (total >= (1ull << 31)) return bh::fail(BH_UNSUP, std::string(what) + ": too many K iterations");
-    // splits 1..4: blocks per CU, iterations dealt equally (tiles cut between blocks);
-    // 5..8: blocks per CU 1..4, whole tiles per block (a persistent data-parallel grid whose
-    // DMA ring runs on across tiles: short-K ops, where cut tiles cost more than balance)
-    const bool whole = ch.splits > 4;
-    uint32_t bpc = ch.splits ? std::min<uint32_t>(whole ? ch.splits - 4 : ch.splits, 4)
-                             : std::max(1, std::min(2, 163840 / c.lds_bytes));
-    uint64_t G = (uint64_t)ncu * bpc;
-    uint32_t ipb = (uint32_t)((total + G - 1) / G);
-    if (whole) ipb = (uint32_t)((nblk + G - 1) / G) * ipt;
-    G = (total + ipb - 1) / ipb;
+    if (nblk * ipt >= (1ull << 31)) return bh::fail(BH_UNSUP, std::string(what) + ": too many K iterations");
+    const uint32_t dflt_bpc = (uint32_t)std::max(1, std::min(2, 163840 / c.lds_bytes));
+    const bh::sk_grid g = bh::plan_sk_grid(nblk, ipt, ncu, ch.splits, dflt_bpc, 4);
     p.ipt = ipt;
-    p.ipb = ipb;
-    p.total_it = (uint32_t)total;
+    p.ipb = g.ipb;
+    p.total_it = (uint32_t)g.total;
     set_fd(ipt, p.ipt_m, p.ipt_s);
     set_fd(p.tiles_m, p.tm_m, p.tm_s);
-    int rc = ensure_ws(ctx, (size_t)2 * G * c.BM * c.BN * 4);
-    if (rc == BH_OK) rc = ensure_cnt(ctx, nblk);
-    if (rc != BH_OK) return rc;
-    p.ws = ws_of(ctx);
-    p.cnt = cnt_of(ctx);
+    if (int rc = bh::scratch(ctx, (size_t)2 * g.G * c.BM * c.BN * 4, nblk, sc)) return rc;
+    p.ws = sc.ws;
+    p.cnt = sc.cnt;
     void *args[] = {&p};
-    return bh::launch(ctx, (const void *)k, dim3((uint32_t)G, 1, 1), dim3(c.NT), args, first, true, what);
+    return bh::launch(ctx, (const void *)k, dim3((uint32_t)g.G, 1, 1), dim3(c.NT), args, first, true, what);
   }
   const uint32_t S = resolve_splits(c, ch, p.M, p.N, p.K, ncu);
   const uint32_t nkt = (p.K + c.BK - 1) / c.BK;
@@ -1021,13 +996,12 @@ int launch_gemm(bh_ctx *ctx, int op, choice_t const &ch, int ald, int bld, GemmA
   if (!k) return bh::fail(BH_ERR, std::string(what) + ": loader combination not instantiated");
   void *args[] = {&p};
   if (S > 1) {
-    int rc = ensure_ws(ctx, (size_t)S * nblk * c.BM * c.BN * 4);
+    // the in-kernel combine takes tickets; the reduce kernel needs none
+    int rc = bh::scratch(ctx, (size_t)S * nblk * c.BM * c.BN * 4, red == 2 ? nblk : 0, sc);
     if (rc != BH_OK) return rc;
-    p.ws = ws_of(ctx);
+    p.ws = sc.ws;
     if (red == 2) {
-      rc = ensure_cnt(ctx, nblk);
-      if (rc != BH_OK) return rc;
-      p.cnt = cnt_of(ctx);
+      p.cnt = sc.cnt;
       return bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, true, what);
     }
     rc = bh::launch(ctx, (const void *)k, dim3((uint32_t)nblk, S, 1), dim3(c.NT), args, first, false, what);
@@ -1286,10 +1260,11 @@ int launch_conv(bh_ctx *ctx, const conv_call &cc) {
     if (banks_floats(OC, IC, KY, KX, need) * 4 >= 0x7fffffc0ull || in_bytes >= (1ull << 30))
       return tile(heuristic(1, d, false), p, first);
     if (!pack) {
-      int rc = ensure_wpack(ctx, banks_floats(OC, IC, KY, KX, pack_banks) * 4);
-      if (rc == BH_OK) rc = launch_pack_banks(ctx, cc.filts, (float *)ctx->wpack, OC, IC, KY, KX, pack_banks, first, false);
+      float *mine = nullptr;
+      int rc = bh::pack_buffer(ctx, banks_floats(OC, IC, KY, KX, pack_banks) * 4, mine);
+      if (rc == BH_OK) rc = launch_pack_banks(ctx, cc.filts, mine, OC, IC, KY, KX, pack_banks, first, false);
       if (rc != BH_OK) return rc;
-      pack = (const float *)ctx->wpack;
+      pack = mine;
       repacked = true;
     }
     const bool kfirst = !repacked;  // the main kernel is the call's first dispatch

@@ -3,6 +3,7 @@
 // kernels). Internal to libboda_hip.so.
 #pragma once
 #include "bh_common.h"
+#include "bh_skgrid.h"
 
 namespace bhk {
 
@@ -93,11 +94,17 @@ __device__ __forceinline__ float ld1(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
 }
 
+// Logical block of hardware block bid in a grid of G: blocks b, b + 8, ... share an XCD under the
+// hardware's round-robin placement, so each XCD gets a contiguous run of logical blocks (its L2 sees
+// neighbouring tiles).
+__device__ __forceinline__ uint32_t xcd_contig(uint32_t bid, uint32_t G) {
+  const uint32_t xcd = bid & 7, q = G >> 3, r = G & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 __device__ __forceinline__ void map_tile(uint32_t bid, uint32_t tiles_m, uint32_t tiles_n, uint32_t &tm,
                                          uint32_t &tn) {
-  uint32_t nwg = tiles_m * tiles_n;
-  uint32_t xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  uint32_t wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  uint32_t wgid = xcd_contig(bid, tiles_m * tiles_n);
   const uint32_t G = 8;
   uint32_t per_group = G * tiles_n;
   uint32_t group = wgid / per_group;
@@ -460,21 +467,9 @@ int launch_pack_banks(bh_ctx *ctx, const float *filts, float *packed, uint32_t O
 int launch_wino_pack(bh_ctx *ctx, const float *filts, float *u, uint32_t OC, uint32_t IC, bool first, bool last);
 // floats of the k-major bank (the first part of every pack)
 size_t kmajor_floats(uint32_t OC, uint32_t IC, uint32_t KY, uint32_t KX);
-// split-K / stream-K workspace and arrival tickets of the context (bh_gemm.hip)
-// Inside a captured narrow op these are the scratch of the lane the op runs on (bh_common.h, capture
-// lanes): read the pointers through ws_of / cnt_of after the ensure_* call, never from the context.
-int ensure_ws(bh_ctx *ctx, size_t bytes);
-int ensure_cnt(bh_ctx *ctx, uint64_t n);
-inline float *ws_of(bh_ctx *ctx) {
-  const bh::op_scope *s = ctx->sched.scope;
-  return (float *)(s && s->lane > 0 ? ctx->sched.lane[s->lane].ws : ctx->ws);
-}
-inline uint32_t *cnt_of(bh_ctx *ctx) {
-  const bh::op_scope *s = ctx->sched.scope;
-  return (uint32_t *)(s && s->lane > 0 ? ctx->sched.lane[s->lane].cnt : ctx->cnt);
-}
 int launch_xpose_filts(bh_ctx *ctx, const float *w, float *wp, uint32_t OC, uint32_t IC, uint32_t KYX, bool first,
                        bool last);
-int ensure_wpack(bh_ctx *ctx, size_t bytes);
+// a tensor of this many bytes is addressable through a buffer resource (every offset below OOB)
+inline bool fits_buffer(uint64_t bytes) { return bytes < (uint64_t)OOB - 64; }
 
 }  // namespace bhk

@@ -429,12 +429,8 @@ __global__ __launch_bounds__(128 * WGM) void ring_kernel(GemmArgs p) {
 //    ticket, and the last arriver sums the slabs in k order (block b0..b1) and stores -- the
 //    same fixed-order rule as the split-K combine, so results are bitwise reproducible.
 // Logical blocks are laid out XCD-contiguously (hardware deals blocks round-robin over the
-// 8 XCDs), so each XCD's L2 sees a contiguous run of tiles.
+// 8 XCDs), so each XCD's L2 sees a contiguous run of tiles (xcd_contig).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t xcd_contig(uint32_t bid, uint32_t G) {
-  const uint32_t xcd = bid & 7, q = G >> 3, r = G & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 // tile index -> (tile_m, tile_n), m fastest: consecutive tiles of a block share the B
 // (input) column panel, the big operand of a convolution
 __device__ __forceinline__ void sk_tile_coords(const GemmArgs &p, uint32_t t, uint32_t &tm, uint32_t &tn) {
@@ -995,10 +991,6 @@ int launch_pack_banks(bh_ctx *ctx, const float *filts, float *packed, uint32_t O
                        : launch_wx_pack(ctx, filts, u, OC, IC, b == BANK_W25 ? 5 : 3, false, lb);
   }
   return rc;
-}
-
-int ensure_wpack(bh_ctx *ctx, size_t bytes) {
-  return bh::lane_wpack(ctx, bytes);
 }
 
 }  // namespace bhk

@@ -39,7 +39,7 @@ int check_launch(const char *what) {
   return BH_OK;
 }
 
-int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, const char *what) {
+int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, const char *what, bool headroom) {
   if (have >= want) return BH_OK;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   BH_HIP(hipStreamIsCapturing(ctx->stream, &st));
@@ -58,7 +58,7 @@ int grow_buffer(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero, c
     buf = nullptr;
     have = 0;
   }
-  const size_t sz = want + (want >> 2);
+  const size_t sz = headroom ? want + (want >> 2) : want;
   BH_HIP(hipMalloc(&buf, sz));
   if (zero) BH_HIP(hipMemsetAsync(buf, 0, sz, ctx->stream));
   have = sz;
@@ -79,9 +79,6 @@ op_scope::op_scope(bh_ctx *ctx, double flops, double bytes) : c(ctx) {
 }
 
 namespace {
-// the stream of lane k of the running capture
-hipStream_t lane_stream(bh_ctx *ctx, int k) { return k > 0 ? ctx->sched.lane[k].stream : ctx->stream; }
-
 int next_event(bh_ctx *ctx, hipEvent_t &ev) {
   bh_sched &sc = ctx->sched;
   if (sc.ev_used == sc.ev.size()) {
@@ -118,26 +115,6 @@ int join_streams(bh_ctx *ctx) {
   if (any) ++sc.cur[2];
   return rc;
 }
-
-int grow_lane(bh_ctx *ctx, void *&buf, size_t &have, size_t want, bool zero) {
-  if (have >= want) return BH_OK;
-  if (buf) {  // as grow_buffer: a captured graph may still replay this pointer
-    bool live_graph = false;
-    for (hipGraphExec_t g : ctx->graphs) live_graph |= g != nullptr;
-    if (live_graph) {
-      ctx->retired.push_back(buf);
-    } else {
-      BH_HIP(hipStreamSynchronize(ctx->stream));
-      BH_HIP(hipFree(buf));
-    }
-  }
-  buf = nullptr;
-  have = 0;
-  BH_HIP(hipMalloc(&buf, want));
-  if (zero) BH_HIP(hipMemsetAsync(buf, 0, want, ctx->stream));
-  have = want;
-  return BH_OK;
-}
 }  // namespace
 
 int barrier(bh_ctx *ctx) {
@@ -158,8 +135,7 @@ int lane_resolve(bh_ctx *ctx, size_t ws_need) {
     if (!s->narrow) {  // a wide op has the device to itself, on the context's stream
       if (int rc = barrier(ctx)) return rc;
     } else {
-      // scratch never grows inside a capture: an op that needs more than a side lane holds takes
-      // lane 0 and the context's own scratch
+      // scratch never grows inside a capture: an op that needs more than a side lane holds takes lane 0
       p = sc.trk.place(s->acc, s->est_us, (s->pin0 || ws_need > sc.lane[1].ws_bytes) ? 0 : -1);
       if (p.join_first)
         if (int rc = join_streams(ctx)) return rc;
@@ -167,56 +143,61 @@ int lane_resolve(bh_ctx *ctx, size_t ws_need) {
   }
   sc.used_mask |= 1u << p.lane;
   sc.cur_trace.push_back((uint32_t)p.lane | p.wait_mask << 8);
-  hipStream_t mine = lane_stream(ctx, p.lane);
-  if (p.lane > 0 && !sc.lane[p.lane].forked) {  // the lane's first use since the last join: fork
-    sc.lane[p.lane].forked = true;
-    if (int rc = order_after(ctx, ctx->stream, mine)) return rc;
+  bh_lane &l = sc.lane[p.lane];
+  if (l.stream != ctx->stream && !l.forked) {  // a side lane's first use since the last join: fork
+    l.forked = true;
+    if (int rc = order_after(ctx, ctx->stream, l.stream)) return rc;
   }
   for (int j = 0; j < sc.lanes; ++j)
     if (p.wait_mask >> j & 1) {
       ++sc.cur[1];
-      if (int rc = order_after(ctx, lane_stream(ctx, j), mine)) return rc;
+      if (int rc = order_after(ctx, sc.lane[j].stream, l.stream)) return rc;
     }
   s->lane = p.lane;  // from here on the call's launches and scratch are this lane's
   return BH_OK;
 }
 
-int lane_ws(bh_ctx *ctx, size_t bytes) {
+int scratch(bh_ctx *ctx, size_t ws_bytes, uint64_t tickets, scratch_t &out) {
   bh_sched &sc = ctx->sched;
-  if (int rc = lane_resolve(ctx, bytes)) return rc;
-  if (sc.scope && sc.scope->lane > 0) {
-    if (bytes <= sc.lane[sc.scope->lane].ws_bytes) return BH_OK;
-    return fail(BH_ERR, "split-K workspace: the per-lane workspace must grow (" + std::to_string(bytes) +
-                            " bytes) while the stream is being captured; run this op once eagerly before capturing");
+  if (int rc = lane_resolve(ctx, ws_bytes)) return rc;
+  const op_scope *s = sc.scope;
+  const int k = s ? s->lane : 0;
+  bh_lane &l = sc.lane[k];
+  if (k != 0) {
+    // a side lane runs inside a capture only, where nothing grows: it holds what bh_capture_begin gave it
+    if (ws_bytes > l.ws_bytes)
+      return fail(BH_ERR, "split-K workspace: the per-lane workspace must grow (" + std::to_string(ws_bytes) +
+                              " bytes) while the stream is being captured; run this op once eagerly before capturing");
+    if (tickets > l.cnt_n)
+      return fail(BH_ERR, "split-K tickets: the per-lane tickets must grow (" + std::to_string(tickets) +
+                              ") while the stream is being captured; run this op once eagerly before capturing");
+  } else {
+    if (ws_bytes) {
+      if (!sc.capturing && s && s->narrow) sc.hw_ws = std::max(sc.hw_ws, ws_bytes);
+      if (int rc = grow_buffer(ctx, l.ws, l.ws_bytes, ws_bytes, false, "split-K workspace")) return rc;
+    }
+    if (tickets) {
+      size_t have = l.cnt_n * 4;
+      const int rc = grow_buffer(ctx, l.cnt, have, std::max<uint64_t>(tickets, 4096) * 4, true, "split-K tickets");
+      l.cnt_n = have / 4;
+      if (rc != BH_OK) return rc;
+    }
   }
-  if (!sc.capturing && sc.scope && sc.scope->narrow) sc.hw_ws = std::max(sc.hw_ws, bytes);
-  return grow_buffer(ctx, ctx->ws, ctx->ws_bytes, bytes, false, "split-K workspace");
+  out.ws = ws_bytes ? (float *)l.ws : nullptr;
+  out.cnt = tickets ? (uint32_t *)l.cnt : nullptr;
+  return BH_OK;
 }
 
-int lane_cnt(bh_ctx *ctx, uint64_t n) {
+int pack_buffer(bh_ctx *ctx, size_t bytes, float *&out) {
   bh_sched &sc = ctx->sched;
-  if (int rc = lane_resolve(ctx, 0)) return rc;
-  if (sc.scope && sc.scope->lane > 0) {
-    // side lanes hold as many tickets as the context did when the capture began
-    if (n <= sc.lane[sc.scope->lane].cnt_n) return BH_OK;
-    return fail(BH_ERR, "split-K tickets: the per-lane tickets must grow (" + std::to_string(n) +
-                            ") while the stream is being captured; run this op once eagerly before capturing");
-  }
-  size_t have = ctx->cnt_n * 4;
-  int rc = grow_buffer(ctx, ctx->cnt, have, std::max<uint64_t>(n, 4096) * 4, true, "split-K tickets");
-  ctx->cnt_n = have / 4;
-  return rc;
-}
-
-int lane_wpack(bh_ctx *ctx, size_t bytes) {
-  bh_sched &sc = ctx->sched;
-  int rc = grow_buffer(ctx, ctx->wpack, ctx->wpack_bytes, bytes, false, "filter-bank pack buffer");
-  if (rc != BH_OK || !sc.capturing || !sc.scope) return rc;
+  if (int rc = grow_buffer(ctx, ctx->wpack, ctx->wpack_bytes, bytes, false, "filter-bank pack buffer")) return rc;
+  out = (float *)ctx->wpack;
+  if (!sc.capturing || !sc.scope) return BH_OK;
   // one pack buffer per context: the op writes then reads it, so it conflicts with every other
   // outstanding op that repacks
   if (sc.scope->resolved) return fail(BH_ERR, "filter-bank pack buffer requested after the call's lane was picked");
   sc.scope->write(ctx->wpack, ctx->wpack_bytes);
-  sc.scope->pin0 = true;  // and its other scratch is the context's, as its pack buffer
+  sc.scope->pin0 = true;  // and its other scratch is lane 0's, as its pack buffer
   return BH_OK;
 }
 
@@ -226,7 +207,7 @@ int launch(bh_ctx *ctx, const void *kernel, dim3 grid, dim3 block, void **args, 
   if (ctx->sched.capturing) {
     // a scoped call's kernels go to its lane; anything else runs behind all lanes
     if (int rc = ctx->sched.scope ? lane_resolve(ctx, 0) : barrier(ctx)) return rc;
-    if (ctx->sched.scope) stream = lane_stream(ctx, ctx->sched.scope->lane);
+    if (ctx->sched.scope) stream = ctx->sched.lane[ctx->sched.scope->lane].stream;
   }
   hipEvent_t b = first ? ctx->t_start : nullptr, e = last ? ctx->t_stop : nullptr;
   hipError_t r = (b || e) ? hipExtLaunchKernel(kernel, grid, block, args, shmem, stream, b, e, 0)
@@ -306,7 +287,6 @@ int bh_init(int device, bh_ctx **out) {
     delete c;
     return bh::fail(BH_ERR, "device is " + arch + "; libboda_hip is built for gfx950 (MI355X) only");
   }
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipMalloc(&c->stamps, STAMP_SLOTS * sizeof(unsigned long long));
   if (e == hipSuccess) {
     int khz = 0;
@@ -326,15 +306,15 @@ int bh_init(int device, bh_ctx **out) {
   if (const char *v = getenv("GPU_MAX_HW_QUEUES"))
     if (atoi(v) < 4) sc.lanes = 1;
   sc.lanes = std::max(1, std::min(sc.lanes, (int)bh_lanes::MAX_LANES));
-  for (int k = 1; k < sc.lanes && e == hipSuccess; ++k)
+  for (int k = 0; k < sc.lanes && e == hipSuccess; ++k)
     e = hipStreamCreateWithFlags(&sc.lane[k].stream, hipStreamNonBlocking);
+  c->stream = sc.lane[0].stream;
   sc.trk.reset(sc.lanes);
   sc.trk.set_fork_us(fork_us);
   if (e != hipSuccess) {
-    for (int k = 1; k < bh_lanes::MAX_LANES; ++k)
-      if (sc.lane[k].stream) (void)hipStreamDestroy(sc.lane[k].stream);
+    for (bh_lane &l : sc.lane)
+      if (l.stream) (void)hipStreamDestroy(l.stream);
     if (c->stamps) (void)hipFree(c->stamps);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return bh::fail(BH_ERR, std::string("bh_init: ") + hipGetErrorString(e));
   }
@@ -351,20 +331,16 @@ int bh_destroy(bh_ctx *c) {
     if (g) (void)hipGraphExecDestroy(g);
   bh::jit_release_all(c);
   for (void *r : c->retired) (void)hipFree(r);
-  if (c->ws) (void)hipFree(c->ws);
   if (c->wpack) (void)hipFree(c->wpack);
   if (c->bckw) (void)hipFree(c->bckw);
   if (c->stamps) (void)hipFree(c->stamps);
-  if (c->cnt) (void)hipFree(c->cnt);
-  for (int k = 1; k < bh_lanes::MAX_LANES; ++k) {
-    bh_lane &l = c->sched.lane[k];
+  for (bh_lane &l : c->sched.lane) {
     if (l.stream) (void)hipStreamSynchronize(l.stream);
     if (l.ws) (void)hipFree(l.ws);
     if (l.cnt) (void)hipFree(l.cnt);
     if (l.stream) (void)hipStreamDestroy(l.stream);
   }
   for (hipEvent_t ev : c->sched.ev) (void)hipEventDestroy(ev);
-  (void)hipStreamDestroy(c->stream);
   delete c;
   return BH_OK;
 }
@@ -763,13 +739,14 @@ int bh_capture_begin(bh_ctx *c) {
   BH_ENTER(c);
   bh_sched &sc = c->sched;
   if (sc.capturing) return bh::fail(BH_ERR, "bh_capture_begin: the context is already capturing");
-  // side-lane scratch never grows inside a capture: bring it up to what eager narrow ops asked for
-  // (workspace) and to the context's own tickets (zero-filled, as the context's) now
-  for (int k = 1; k < sc.lanes; ++k) {
+  // scratch never grows inside a capture: bring every lane up to what eager narrow ops asked for
+  // (workspace) and to lane 0's tickets (zero-filled, as lane 0's) now, without headroom. Lane 0 served
+  // those eager ops: it holds both already.
+  for (int k = 0; k < sc.lanes; ++k) {
     bh_lane &l = sc.lane[k];
-    if (int rc = bh::grow_lane(c, l.ws, l.ws_bytes, sc.hw_ws, false)) return rc;
+    if (int rc = bh::grow_buffer(c, l.ws, l.ws_bytes, sc.hw_ws, false, "split-K workspace", false)) return rc;
     size_t have = l.cnt_n * 4;
-    int rc = bh::grow_lane(c, l.cnt, have, c->cnt_n * 4, true);
+    int rc = bh::grow_buffer(c, l.cnt, have, sc.lane[0].cnt_n * 4, true, "split-K tickets", false);
     l.cnt_n = have / 4;
     if (rc != BH_OK) return rc;
     l.forked = false;
@@ -795,7 +772,7 @@ int bh_capture_end(bh_ctx *c, int *graph_id) {
   const std::string jmsg = jrc == BH_OK ? std::string() : std::string(bh_last_error());
   sc.capturing = false;
   sc.trk.join();
-  for (int k = 1; k < sc.lanes; ++k) sc.lane[k].forked = false;
+  for (bh_lane &l : sc.lane) l.forked = false;
   BH_HIP(hipStreamEndCapture(c->stream, &g));
   if (jrc != BH_OK) {
     if (g) (void)hipGraphDestroy(g);

@@ -149,13 +149,6 @@ __device__ __forceinline__ void at_row(const float *x, float *y) {
   }
 }
 
-// logical block of hardware block bid: blocks b, b + 8, ... share an XCD under round-robin placement,
-// so each XCD gets a contiguous run of units (the same OC tiles' U slices in its L2)
-__device__ __forceinline__ uint32_t wx_lb(uint32_t bid, uint32_t G) {
-  const uint32_t xcd = bid & 7, q = G >> 3, r = G & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // DBG (diagnostic builds in the instrumented library only; wrong results by design): bit 0 = no input
 // transform in the stage loop, 1 = no MFMA, 2 = no strip DMA, 3 = no U loads, 4 = no V fragment
 // loads, 5 = no stage barrier
@@ -188,7 +181,8 @@ __global__ __launch_bounds__(64 * NW, 2) void wgx_kernel(WxArgs p) {
   // (SK 2: the hardware's dispatch order itself -- the whole units go out first, spread over all
   // XCDs, and the tail pieces fill the CUs as they free; the XCD-contiguous remap would hand some XCDs
   // only whole units and others only pieces)
-  const uint32_t lb = SK >= 2 ? blockIdx.x : wx_lb(blockIdx.x, gridDim.x);
+  // (each XCD a contiguous run of units: the same OC tiles' U slices in its L2)
+  const uint32_t lb = SK >= 2 ? blockIdx.x : xcd_contig(blockIdx.x, gridDim.x);
   // SK 3: a tail piece computes only channel group `piece` of its unit (the other waves transform,
   // load and synchronise as usual but issue no MFMA and no U load, and store nothing)
   const int piece = (SK == 3 && lb >= p.ipb) ? (int)((lb - p.ipb) % p.total_it) : -1;
@@ -1024,6 +1018,7 @@ static int launch_wgx(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, Gemm
   const void *k = (const void *)c.k[A_KVEC][B_DIRECT][0];
   if (int rc = bh::dyn_lds(k, lds, "conv: Winograd LDS attribute")) return rc;
   uint32_t G = (uint32_t)units;
+  bh::scratch_t sc;
   // blocks resident at once (the split forms' rounds)
   const uint64_t C = c.sk ? (uint64_t)bh::num_cus(ctx) * (uint32_t)std::min(bh::occupancy(k, (int)XNT, (size_t)lds), 2) : 0;
   if (c.sk == 3) {
@@ -1050,11 +1045,7 @@ static int launch_wgx(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, Gemm
       p.total_it = S;
       G = (uint32_t)(R * C + T * S);
       const size_t slab = (size_t)(16 / (XNT / ((XNT / 64 / NPG) * 64))) * XNT * MO * MO;
-      int rc = ensure_ws(ctx, (size_t)2 * G * slab * 4);
-      if (rc == BH_OK) rc = ensure_cnt(ctx, units);
-      if (rc != BH_OK) return rc;
-      p.ws = ws_of(ctx);
-      p.cnt = cnt_of(ctx);
+      if (int rc = bh::scratch(ctx, (size_t)2 * G * slab * 4, units, sc)) return rc;
     }
   } else if (c.sk) {
     // stream-K: as many blocks as are resident at once, the (unit, stage) iterations dealt equally
@@ -1064,12 +1055,10 @@ static int launch_wgx(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, Gemm
     G = (uint32_t)((total + p.ipb - 1) / p.ipb);
     p.total_it = (uint32_t)total;
     const size_t slab = (size_t)(16 / (XNT / ((XNT / 64 / NPG) * 64))) * XNT * MO * MO;  // NR * NT * MO^2 floats
-    int rc = ensure_ws(ctx, (size_t)2 * G * slab * 4);
-    if (rc == BH_OK) rc = ensure_cnt(ctx, units);
-    if (rc != BH_OK) return rc;
-    p.ws = ws_of(ctx);
-    p.cnt = cnt_of(ctx);
+    if (int rc = bh::scratch(ctx, (size_t)2 * G * slab * 4, units, sc)) return rc;
   }
+  p.ws = sc.ws;  // null where the form cuts no unit
+  p.cnt = sc.cnt;
   bh::set_trace(ctx, p);
   void *args[] = {&p};
   // splits 20 on a stream-K configuration: the cut units summed by wx_combine_kernel (a second launch)

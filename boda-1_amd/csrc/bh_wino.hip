@@ -103,13 +103,6 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const float *__restrict_
   }
 }
 
-// logical block of hardware block bid: blocks b, b+8, ... share an XCD under round-robin
-// placement, so each XCD gets a contiguous run of iterations (neighbouring tiles in its L2)
-__device__ __forceinline__ uint32_t wg_lb(uint32_t bid, uint32_t G) {
-  const uint32_t xcd = bid & 7, q = G >> 3, r = G & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
-
 // x where the lane's bit of m is set, else 0 (one v_cndmask against a wave mask held in SGPRs)
 __device__ __forceinline__ float wg_lane_sel(uint64_t m, float x) {
   float r;
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(64 * NWO * NWT) void wgp_kernel(WgArgs p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wo = wave % NWO, wtl = wave / NWO;
   const int li = lane & 31, kh = lane >> 5;
-  const uint32_t lb = wg_lb(blockIdx.x, gridDim.x);
+  const uint32_t lb = xcd_contig(blockIdx.x, gridDim.x);
   const uint32_t it0 = lb * p.ipb, it1 = min(p.total_it, it0 + p.ipb);
   if (tid < D * GZ) smem[(tid / GZ) * SLOT + tid % GZ] = 0.0f;
 
@@ -1074,23 +1067,18 @@ static int launch_wg(bh_ctx *ctx, const cfg_t &c, const bh::conv_call &cc, GemmA
   if (splits >= 10) splits -= 10;
   p.ngr = ngroups;
   bh::set_fd(ngroups, p.ngr_m, p.ngr_s);
-  const bool whole = splits > 4;
-  uint32_t bpc = splits ? (whole ? splits - 4 : splits) : 1;
-  bpc = std::max(1u, std::min<uint32_t>(bpc, (uint32_t)std::min(occ, 4)));
-  uint64_t G = (uint64_t)bh::num_cus(ctx) * bpc;
-  uint32_t ipb = (uint32_t)((total + G - 1) / G);
-  if (whole) ipb = (uint32_t)((ntile + G - 1) / G) * ipt;
-  G = (total + ipb - 1) / ipb;
-  p.ipb = ipb;
+  const bh::sk_grid g = bh::plan_sk_grid(ntile, ipt, bh::num_cus(ctx), splits, 1, (uint32_t)std::min(occ, 4));
+  const uint64_t G = g.G;
+  p.ipb = g.ipb;
   p.total_it = (uint32_t)total;
-  int rc = ensure_ws(ctx, (size_t)2 * G * NT * 16 * 16);  // two slabs of 16 float4 per thread per block
-  if (rc == BH_OK) rc = ensure_cnt(ctx, (size_t)ntile);
+  bh::scratch_t sc;
+  int rc = bh::scratch(ctx, (size_t)2 * G * NT * 16 * 16, ntile, sc);  // two slabs of 16 float4 per thread per block
   if (rc != BH_OK) return rc;
-  p.ws = ws_of(ctx);
-  p.cnt = cnt_of(ctx);
+  p.ws = sc.ws;
+  p.cnt = sc.cnt;
   bh::set_trace(ctx, p);
   void *args[] = {&p};
-  if (whole) p.sepc = 0;  // no cut tiles
+  if (splits > 4) p.sepc = 0;  // whole tiles per block: no cut tiles
   if (!p.sepc) return bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(NT), args, first, true, "conv_wino", lds);
   rc = bh::launch(ctx, k, dim3((uint32_t)G, 1, 1), dim3(NT), args, first, false, "conv_wino", lds);
   if (rc != BH_OK) return rc;

@@ -212,6 +212,27 @@ def test_split_k_ops_on_different_lanes_have_their_own_scratch():
     assert sorted(l for l, _ in trace) == [0, 1, 2] and edges == 0, trace  # two of them on side lanes
 
 
+@pytest.mark.parametrize("name", ["srk128x64x32d4", "dm3w16x64c8", "wgp64x64", "wx23s4k"])
+def test_persistent_families_take_their_scratch_from_their_lane(name):
+    """One forced configuration of each persistent stream-K family (ring, direct, Winograd, position-split
+    Winograd) on a conv small enough that every output tile is cut between blocks: partial tiles meet in
+    the workspace and the tickets decide who sums them, so copies of the op on different lanes give the
+    eager bits only with scratch of their own. (With an override set a configuration that rejects the
+    shape fails the call: nothing else can have run.)"""
+    s = ops.ConvShape(2, 32, 14, 14, 96, 3, 3, 1, 1, 1, 1)
+    with lanes_device(4, 50.0) as d:
+        wl = runner.Workload(d, [s] * 3)
+        d.tune_set(1, boda_hip.tune_cfg_names(1).index(name), 0)
+        try:
+            assert name in d.variant(1, s.as_dims())
+            eager, got, (lanes, edges, joins, nops), trace = eager_then_replay(d, wl)
+        finally:
+            d.tune_set(1, -1, 0)
+            wl.free()
+    assert_same(eager, got)
+    assert nops == 3 and len({l for l, _ in trace}) >= 2, (lanes, edges, joins, nops, trace)
+
+
 def test_short_run_of_ops_stays_one_chain():
     """A side lane costs a fork and a join: below BH_CAPTURE_FORK_US of estimated work the ops stay on
     the context's stream (SHAPES[:5] count as 20 us, each op as its roofline time or 2 us; all of SHAPES
