@@ -32,8 +32,12 @@ EXPORTS = ["bh_abi_version", "bh_last_error", "bh_device_count", "bh_init", "bh_
            "bh_jit_launch", "bh_jit_release", "bh_conv_filts_packed_floats_banks", "bh_conv_filts_pack_banks",
            "bh_conv_route_banks", "bh_conv2d_fwd_nchw_pkb", "bh_conv_bck_filts_packed_floats",
            "bh_conv_bck_filts_pack", "bh_conv2d_bck_in_nchw", "bh_conv2d_bck_filts_nchw", "bh_conv2d_bck_biases",
-           "bh_conv2d_bck_nchw", "bh_capture_stats", "bh_capture_trace"]
+           "bh_conv2d_bck_nchw", "bh_capture_stats", "bh_capture_trace", "bh_spreading_nchw", "bh_lrn_bck_nchw",
+           "bh_zero_if_non_pos", "bh_reduce_sum", "bh_sm_grad_and_loss", "bh_sum_loss_over_imgs",
+           "bh_softmax_with_loss"]
+FORM_PROD, FORM_REF64 = 0, 1  # the last argument of the backward-op entries (bh_bckops.hip)
 GEN_BCK_OUT_GRAD = 5
+GEN_COND, GEN_LABEL = 6, 7
 BANK_W23, BANK_W43, BANK_W25, BANKS_ALL = 1, 2, 4, 0xffffffff
 
 
@@ -105,6 +109,13 @@ def lib():
         L.bh_chan_copy.argtypes = [c_vp, c_vp, c_vp] + [c_u32] * 7
         L.bh_chan_affine.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp] + [c_u32] * 3 + [ctypes.c_int]
         L.bh_eltwise.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int]
+        L.bh_spreading_nchw.argtypes = [c_vp] * 4 + [c_u32] * 10 + [ctypes.c_int] * 2
+        L.bh_lrn_bck_nchw.argtypes = [c_vp] * 6 + [c_u32] * 5 + [ctypes.c_float] * 3 + [ctypes.c_int]
+        L.bh_zero_if_non_pos.argtypes = [c_vp] * 4 + [ctypes.c_uint64, ctypes.c_int]
+        L.bh_reduce_sum.argtypes = [c_vp, ctypes.POINTER(c_vp), c_u32, c_vp, ctypes.c_uint64, ctypes.c_int]
+        L.bh_sm_grad_and_loss.argtypes = [c_vp] * 5 + [c_u32] * 4 + [ctypes.c_int]
+        L.bh_sum_loss_over_imgs.argtypes = [c_vp] * 3 + [c_u32] * 2 + [ctypes.c_int]
+        L.bh_softmax_with_loss.argtypes = [c_vp] * 7 + [c_u32] * 4 + [ctypes.c_int]
         L.bh_variant_name.argtypes = [ctypes.c_int, ctypes.POINTER(c_u32), ctypes.c_char_p, ctypes.c_size_t]
         L.bh_variant_name_ctx.argtypes = [c_vp, ctypes.c_int, ctypes.POINTER(c_u32), ctypes.c_char_p, ctypes.c_size_t]
         L.bh_stamp.argtypes = [c_vp, ctypes.c_int]
@@ -386,6 +397,37 @@ class Device:
 
     def eltwise(self, a, b, out, n, op=1, relu=0):
         _check(lib().bh_eltwise(self.ctx, a.ptr, b.ptr, out.ptr, n, op, int(relu)))
+
+    # ---- the backward pass of those layers (bh_bckops.hip); form 0 production, 1 ref64
+    def spreading(self, og, out_in_yx, in_grad, B, C, H, W, KY, KX, sy, sx, py, px, avg, form=0):
+        """bh_spreading_nchw: the backward of pool with the same dims; out_in_yx may be None when avg."""
+        _check(lib().bh_spreading_nchw(self.ctx, og.ptr, out_in_yx.ptr if out_in_yx is not None else None,
+                                       in_grad.ptr, B, C, H, W, KY, KX, sy, sx, py, px, int(avg), form))
+
+    def lrn_bck(self, inp, out, out_scale_base, og, in_grad, B, C, H, W, local_size, alpha, beta, k, form=0):
+        _check(lib().bh_lrn_bck_nchw(self.ctx, inp.ptr, out.ptr, out_scale_base.ptr, og.ptr, in_grad.ptr, B, C, H, W,
+                                     local_size, alpha, beta, k, form))
+
+    def zero_if_non_pos(self, inp, cond, out, n, form=0):
+        """bh_zero_if_non_pos: out = cond > 0 ? in : 0; out may be inp."""
+        _check(lib().bh_zero_if_non_pos(self.ctx, inp.ptr, cond.ptr, out.ptr, n, form))
+
+    def reduce_sum(self, ins, out, n, form=0):
+        """bh_reduce_sum: out = ((0 + ins[0]) + ins[1]) + ... over n elements."""
+        arr = (c_vp * max(1, len(ins)))(*[b.ptr for b in ins])
+        _check(lib().bh_reduce_sum(self.ctx, arr, len(ins), out.ptr, n, form))
+
+    def sm_grad_and_loss(self, prob, label, in_grad, loss_per_pel, B, C, H, W, form=0):
+        _check(lib().bh_sm_grad_and_loss(self.ctx, prob.ptr, label.ptr, in_grad.ptr, loss_per_pel.ptr, B, C, H, W,
+                                         form))
+
+    def sum_loss_over_imgs(self, loss_per_pel, loss, B, HW, form=0):
+        _check(lib().bh_sum_loss_over_imgs(self.ctx, loss_per_pel.ptr, loss.ptr, B, HW, form))
+
+    def softmax_with_loss(self, inp, label, prob, in_grad, loss_per_pel, loss, B, C, H, W, form=0):
+        """bh_softmax_with_loss: softmax, sm_grad_and_loss and sum_loss_over_imgs as one call."""
+        _check(lib().bh_softmax_with_loss(self.ctx, inp.ptr, label.ptr, prob.ptr, in_grad.ptr, loss_per_pel.ptr,
+                                          loss.ptr, B, C, H, W, form))
 
     def conv_filts_pack(self, filts, packed, s, banks=None):
         """Boda's xpose_filts counterpart: write the k-major bank of filts (+ the Winograd banks: all of

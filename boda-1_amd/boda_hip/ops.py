@@ -253,6 +253,154 @@ def bck_bytes(s):
     return 4 * (2 * s.B * s.IC * s.H * s.W + 2 * s.OC * s.K + s.B * s.OC * s.OH * s.OW + s.OC)
 
 
+def pool_out_sz(i, pad, k, stride):
+    """Caffe pooling: a partial last window adds an output (src/conv_util.cc:198-204)."""
+    p = i + 2 * pad
+    return 1 if p < k else -(-(p - k) // stride) + 1
+
+
+@dataclass(frozen=True)
+class BckOpShape:
+    """One backward op of a non-conv layer (bh_bckops.hip): the B x C x H x W tensor its gradient has, and
+    what its type adds: the pooling window (Spreading), local_size (BckLRN), n_ins (Reduce). The work
+    model (op_desc.cc op_work states the same): bytes = 4 x the elements of every tensor
+    the definition reads or writes."""
+    type: str
+    B: int
+    C: int
+    H: int
+    W: int
+    KY: int = 0
+    KX: int = 0
+    sy: int = 0
+    sx: int = 0
+    py: int = 0
+    px: int = 0
+    avg: int = 0
+    local_size: int = 0
+    n_ins: int = 0
+
+    @property
+    def N(self):
+        return self.B * self.C * self.H * self.W
+
+    @property
+    def OH(self):
+        return pool_out_sz(self.H, self.py, self.KY, self.sy)
+
+    @property
+    def OW(self):
+        return pool_out_sz(self.W, self.px, self.KX, self.sx)
+
+    def flops(self):
+        t = self.type
+        if t == "Spreading":  # the windows that can cover a pixel
+            return self.N * -(-self.KY // self.sy) * -(-self.KX // self.sx)
+        return {"ZeroIfNonPos": 0, "BckDropout": self.N, "Reduce": self.n_ins * self.N,
+                "BckLRN": self.N * (self.local_size + 8), "SoftmaxWithLoss": 3 * self.N}[t]
+
+    def bytes(self):
+        t, n = self.type, self.N
+        if t == "Spreading":  # out_grad_loss (+ out_in_yx for max) read, in_grad_loss written
+            return 4 * ((1 if self.avg else 2) * self.B * self.C * self.OH * self.OW + n)
+        if t == "SoftmaxWithLoss":  # in, prob, in_grad_loss; label, loss_per_pel; loss
+            return 4 * (3 * n + 2 * self.B * self.H * self.W + self.H * self.W)
+        # BckLRN: in, out, out_scale_base, out_grad_loss, in_grad_loss; BckDropout is in place
+        return 4 * n * {"ZeroIfNonPos": 3, "BckDropout": 2, "Reduce": self.n_ins + 1, "BckLRN": 5}[t]
+
+    def as_dims(self):
+        d = [self.B, self.C, self.H, self.W]
+        if self.type == "Spreading":
+            d += [self.KY, self.KX, self.sy, self.sx, self.py, self.px, self.avg]
+        elif self.type == "BckLRN":
+            d += [self.local_size]
+        elif self.type == "Reduce":
+            d += [self.n_ins]
+        return d
+
+
+def _nchw(op, name):
+    if name not in op.dims:
+        raise ValueError("%s op without %s dims: %s" % (op.type, name, op.line))
+    d = op.dims[name]
+    if list(d.keys()) != ["img", "chan", "y", "x"]:
+        raise ValueError("%s is not img x chan x y x x: %s" % (name, op.line))
+    return (d["img"], d["chan"], d["y"], d["x"])
+
+
+def _same(op, names, want):
+    for n in names:
+        if _nchw(op, n) != want:
+            raise ValueError("%s dims differ from %s: %s" % (n, "x".join(map(str, want)), op.line))
+
+
+def spreading_shape(op):
+    """Op (type Spreading, src/conv_util.cc:40-64) -> BckOpShape: in_grad_loss has the dims of in, out (if
+    listed) and out_grad_loss are B x C x OH x OW of the pooling size rule; a line without kern_sz
+    pools globally (src/cnn_op.cc:42: the window is in's y x x)."""
+    if op.type != "Spreading":
+        raise ValueError("not a Spreading op: %s" % op.type)
+    B, C, H, W = _nchw(op, "in")
+    for n in ("stride", "in_pad"):
+        if n not in op.dims:
+            raise ValueError("Spreading op without %s dims: %s" % (n, op.line))
+    ks = op.dims.get("kern_sz", {"y": H, "x": W})
+    st, pd = op.dims["stride"], op.dims["in_pad"]
+    s = BckOpShape("Spreading", B, C, H, W, KY=ks["y"], KX=ks["x"], sy=st["y"], sx=st["x"], py=pd["y"], px=pd["x"],
+                   avg=int(op.scalars.get("avg_pool", 0)))
+    if not (s.KY and s.KX and s.sy and s.sx):
+        raise ValueError("zero kern_sz or stride: %s" % op.line)
+    _same(op, ["in_grad_loss"], (B, C, H, W))
+    _same(op, ["out_grad_loss"] + (["out"] if "out" in op.dims else []), (B, C, s.OH, s.OW))
+    return s
+
+
+def bck_lrn_shape(op):
+    """Op (type BckLRN) -> BckOpShape: in, out, out_grad_loss and in_grad_loss have the same dims."""
+    if op.type != "BckLRN":
+        raise ValueError("not a BckLRN op: %s" % op.type)
+    d = _nchw(op, "in")
+    _same(op, ["out", "out_grad_loss", "in_grad_loss"], d)
+    if "local_size" not in op.scalars:
+        raise ValueError("BckLRN op without local_size: %s" % op.line)
+    return BckOpShape("BckLRN", *d, local_size=int(op.scalars["local_size"]))
+
+
+def softmax_loss_shape(op):
+    """Op (type SoftmaxWithLoss) -> BckOpShape: in_grad_loss as in, label img x y x x, loss y x x."""
+    if op.type != "SoftmaxWithLoss":
+        raise ValueError("not a SoftmaxWithLoss op: %s" % op.type)
+    B, C, H, W = d = _nchw(op, "in")
+    _same(op, ["in_grad_loss"], d)
+    for n, want in (("label", [("img", B), ("y", H), ("x", W)]), ("loss", [("y", H), ("x", W)])):
+        if n not in op.dims or list(op.dims[n].items()) != want:
+            raise ValueError("%s dims inconsistent with in: %s" % (n, op.line))
+    return BckOpShape("SoftmaxWithLoss", *d)
+
+
+ELEMENTWISE = {"ZeroIfNonPos": ("in", "cond", "out"), "BckDropout": ("in", "out"), "Reduce": ("out",)}
+
+
+def elementwise_shape(op):
+    """Op (type ZeroIfNonPos / BckDropout / Reduce) -> BckOpShape: every tensor has the same dims; Reduce
+    lists ins_0 .. ins_{n-1}."""
+    if op.type not in ELEMENTWISE:
+        raise ValueError("not an elementwise backward op: %s" % op.type)
+    names = list(ELEMENTWISE[op.type])
+    n_ins = 0
+    if op.type == "Reduce":
+        while "ins_%d" % n_ins in op.dims:
+            n_ins += 1
+        if not n_ins or len(op.dims) != n_ins + 1:
+            raise ValueError("Reduce op needs ins_0 .. ins_n-1 and out: %s" % op.line)
+        names += ["ins_%d" % i for i in range(n_ins)]
+    elif sorted(op.dims) != sorted(names):
+        raise ValueError("%s op needs exactly %s: %s" % (op.type, ", ".join(names), op.line))
+    d = _nchw(op, "out")
+    _same(op, names, d)
+    return BckOpShape(op.type, *d, n_ins=n_ins)
+
+
 def sgemm_shape(op):
     if op.type != "sgemm":
         raise ValueError("not an sgemm op: %s" % op.type)
@@ -282,4 +430,12 @@ def read_ops(path, types=("Convolution", "sgemm")):
 def shape_of(op):
     if op.type == "BckConv":
         return bck_conv_shape(op)
+    if op.type == "Spreading":
+        return spreading_shape(op)
+    if op.type == "BckLRN":
+        return bck_lrn_shape(op)
+    if op.type == "SoftmaxWithLoss":
+        return softmax_loss_shape(op)
+    if op.type in ELEMENTWISE:
+        return elementwise_shape(op)
     return conv_shape(op) if op.type == "Convolution" else sgemm_shape(op)

@@ -142,6 +142,10 @@ inline void set_fd(uint32_t d, uint32_t &m, uint32_t &s) {
   s = f.s;
 }
 
+// blocks of 256 threads that cover n elements, at most cap (grid-stride kernels cover the rest)
+inline uint32_t grid_for(uint64_t n, uint32_t cap = 16384) {
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap));
+}
 inline uint32_t num_cus(const bh_ctx *ctx) {
   return ctx->prop.multiProcessorCount > 0 ? (uint32_t)ctx->prop.multiProcessorCount : 256u;
 }
@@ -259,7 +263,9 @@ int launch_lrn(bh_ctx *ctx, const float *in, float *out, float *out_scale_base, 
                uint32_t W, uint32_t local_size, float alpha, float beta, float k);
 int launch_relu(bh_ctx *ctx, float *x, uint64_t n);
 int launch_dropout(bh_ctx *ctx, float *x, uint64_t n, float ratio, uint32_t seed);
-int launch_softmax(bh_ctx *ctx, const float *in, float *prob, uint32_t B, uint32_t C, uint32_t H, uint32_t W);
+// first / last: whether this is the first / last dispatch of the C-ABI call (bh_time_next_call)
+int launch_softmax(bh_ctx *ctx, const float *in, float *prob, uint32_t B, uint32_t C, uint32_t H, uint32_t W,
+                   bool first = true, bool last = true);
 int launch_chan_copy(bh_ctx *ctx, const float *in, float *out, uint32_t B, uint32_t HW, uint32_t in_c, uint32_t ic0,
                      uint32_t out_c, uint32_t oc0, uint32_t nc);
 int launch_chan_affine(bh_ctx *ctx, const float *in, float *out, const float *scale, const float *shift, uint32_t B,

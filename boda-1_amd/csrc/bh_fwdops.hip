@@ -296,9 +296,7 @@ __global__ __launch_bounds__(256) void eltwise_kernel(const float *__restrict__ 
   }
 }
 
-uint32_t grid_for(uint64_t n, uint32_t cap = 16384) {
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, cap));
-}
+using bh::grid_for;
 
 }  // namespace
 
@@ -387,12 +385,13 @@ int launch_dropout(bh_ctx *ctx, float *x, uint64_t n, float ratio, uint32_t seed
   return launch(ctx, (const void *)dropout_kernel, dim3(grid_for(n)), dim3(256), args, true, true, "dropout");
 }
 
-int launch_softmax(bh_ctx *ctx, const float *in, float *prob, uint32_t B, uint32_t C, uint32_t H, uint32_t W) {
+int launch_softmax(bh_ctx *ctx, const float *in, float *prob, uint32_t B, uint32_t C, uint32_t H, uint32_t W, bool first,
+                   bool last) {
   const uint64_t np = (uint64_t)B * H * W;
   if (np * C >= (1ull << 31)) return fail(BH_UNSUP, "softmax: tensor too large");
   uint32_t npix = (uint32_t)np, HW = H * W;
   void *args[] = {&in, &prob, &npix, &C, &HW};
-  return launch(ctx, (const void *)softmax_kernel, dim3((npix + 255) / 256), dim3(256), args, true, true, "softmax");
+  return launch(ctx, (const void *)softmax_kernel, dim3((npix + 255) / 256), dim3(256), args, first, last, "softmax");
 }
 
 int launch_chan_copy(bh_ctx *ctx, const float *in, float *out, uint32_t B, uint32_t HW, uint32_t in_c, uint32_t ic0,

@@ -10,14 +10,17 @@
 
 namespace {
 
-__device__ __forceinline__ float det_hash_rand(uint32_t rv) {
+__device__ __forceinline__ uint32_t det_hash_u32(uint32_t rv) {
   uint32_t h = rv;
   h ^= h >> 16;
   h *= 0x85ebca6bu;
   h ^= h >> 13;
   h *= 0xc2b2ae35u;
   h ^= h >> 16;
-  return __builtin_fmaf((float)h, 10.0f / 4294967296.0f, -5.0f);
+  return h;
+}
+__device__ __forceinline__ float det_hash_rand(uint32_t rv) {
+  return __builtin_fmaf((float)det_hash_u32(rv), 10.0f / 4294967296.0f, -5.0f);
 }
 
 struct gen_args {
@@ -56,11 +59,15 @@ __device__ __forceinline__ float gen_one(const gen_args &g, uint64_t i) {
     }
     case BH_GEN_CONV_IN:
     case BH_GEN_BCK_OUT_GRAD:
+    case BH_GEN_COND:
     case BH_GEN_CONV_FILTS: {  // img:chan:y:x / out_chan:in_chan:y:x
       uint32_t X = g.d[3], Y = g.d[2];
       uint32_t x = (uint32_t)(i % X), y = (uint32_t)((i / X) % Y);
       // out_grad_loss: gen_data_Convolution_in's modes with a seed of its own
-      uint32_t seed = g.kind == BH_GEN_CONV_IN ? 234234567u : (g.kind == BH_GEN_BCK_OUT_GRAD ? 51283747u : 8753985u);
+      uint32_t seed = g.kind == BH_GEN_CONV_IN        ? 234234567u
+                      : g.kind == BH_GEN_BCK_OUT_GRAD ? 51283747u
+                      : g.kind == BH_GEN_COND         ? 77120563u
+                                                      : 8753985u;
       if (mode == 2) v += (float)x;
       if (mode == 3) v += (float)y;
       else if (mode == 4) { if (x == X / 2 && y == Y / 2) v += 1.0f; }
@@ -69,6 +76,9 @@ __device__ __forceinline__ float gen_one(const gen_args &g, uint64_t i) {
     }
     case BH_GEN_CONV_BIASES:
       if (mode == 5) v += det_hash_rand((uint32_t)i + 39475612u);
+      break;
+    case BH_GEN_LABEL:  // img:y:x, d[3] = C classes: an integer in [0, C), whatever the mode
+      v = (float)(det_hash_u32((uint32_t)i + 90417263u) % g.d[3]);
       break;
   }
   return v;
@@ -109,9 +119,14 @@ int launch_gen_data(bh_ctx *ctx, int kind, float *dst, const uint32_t dims[4], u
       break;
     case BH_GEN_CONV_IN:
     case BH_GEN_BCK_OUT_GRAD:
+    case BH_GEN_COND:
     case BH_GEN_CONV_FILTS:
       for (int i = 0; i < 4; ++i) g.d[i] = dims[i];
       g.n = (uint64_t)dims[0] * dims[1] * dims[2] * dims[3];
+      break;
+    case BH_GEN_LABEL:
+      for (int i = 0; i < 4; ++i) g.d[i] = dims[i];
+      g.n = (uint64_t)dims[0] * dims[1] * dims[2];
       break;
     case BH_GEN_CONV_BIASES:
       g.d[0] = dims[0]; g.d[1] = g.d[2] = g.d[3] = 1;

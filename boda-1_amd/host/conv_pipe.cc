@@ -145,16 +145,16 @@ std::string v2_type(std::string const &t) {
   auto it = m.find(t);
   return it == m.end() ? t : it->second;
 }
-// caffe layer inclusion for the TEST phase (the forward net; caffe NetState default)
-bool included_for_test(pt_msg const &lp) {
+// caffe layer inclusion for a phase (TEST: the forward net, caffe NetState default; TRAIN: add_bck_ops)
+bool included_for(pt_msg const &lp, std::string const &phase) {
   auto phase_of = [](p_pt_msg const &r) { return r ? r->get("phase", "") : std::string(); };
   auto inc = lp.subs("include");
   auto exc = lp.subs("exclude");
   for (auto const &r : exc)
-    if (phase_of(r) == "TEST") return false;
+    if (phase_of(r) == phase) return false;
   if (inc.empty()) return true;
   for (auto const &r : inc)
-    if (phase_of(r).empty() || phase_of(r) == "TEST") return true;
+    if (phase_of(r).empty() || phase_of(r) == phase) return true;
   return false;
 }
 // kernel / stride / pad (y, x) from a convolution_param / pooling_param
@@ -178,7 +178,9 @@ dims_t nchw(uint32_t b, uint32_t c, uint32_t y, uint32_t x) {
 }  // namespace
 
 p_conv_pipe_t create_pipe_from_prototxt(std::string const &text, uint32_t img, std::string const &out_node,
-                                        bool det_dropout) {
+                                        bool det_dropout, bool add_bck_ops) {
+  if (add_bck_ops && !out_node.empty()) rt_err("add_bck_ops needs the whole net: no out node");
+  if (add_bck_ops) det_dropout = true;  // Dropout layers are kept, and must be in place
   p_pt_msg net = parse_prototxt(text);
   auto cp = std::make_shared<conv_pipe_t>();
   cp->name = net->get("name", "net");
@@ -204,7 +206,7 @@ p_conv_pipe_t create_pipe_from_prototxt(std::string const &text, uint32_t img, s
   for (auto const &l : net->subs("layers")) layers.push_back(l);  // V1 nets use `layers`
   bool found_out = false;
   for (auto const &lp : layers) {
-    if (!included_for_test(*lp)) continue;
+    if (!included_for(*lp, add_bck_ops ? "TRAIN" : "TEST")) continue;
     auto op = std::make_shared<conv_op_t>();
     op->tag = lp->get("name");
     op->type = v2_type(lp->get("type"));
@@ -271,9 +273,18 @@ p_conv_pipe_t create_pipe_from_prototxt(std::string const &text, uint32_t img, s
       if (op->tops.empty()) rt_err("Data layer without outputs");
       cp->inputs.push_back(op->tops[0]);
       cp->node_dims[op->tops[0]] = nchw(img ? img : bs, 3, crop, crop);  // src/caffepb.cc: 3-channel crops
+      if (add_bck_ops && op->tops.size() >= 2) {  // the label source node, img:1:1
+        cp->label_node = op->tops[1];
+        cp->inputs.push_back(op->tops[1]);
+        cp->node_dims[op->tops[1]] = dims_t({{"img", img ? img : bs}, {"y", 1}, {"x", 1}});
+      }
       keep = false;
       why = "Data layer (source node " + op->tops[0] + ")";
     } else if (op->type == "ReLU" || op->type == "Concat") {
+    } else if (op->type == "SoftmaxWithLoss" && add_bck_ops) {
+      // in, label -> the gradient of in and the loss (its own top's name, or "loss")
+      if (op->bots.size() != 2) rt_err("layer '" + op->tag + "': SoftmaxWithLoss needs an input and a label");
+      op->tops = {op->bots[0] + "_grad_loss", op->tops.empty() ? std::string("loss") : op->tops[0]};
     } else if (op->type == "Softmax" || op->type == "SoftmaxWithLoss" || op->type == "Accuracy") {
       keep = false;
       why = op->type + " (not part of the forward feature net, as in the reference)";
@@ -292,7 +303,8 @@ p_conv_pipe_t create_pipe_from_prototxt(std::string const &text, uint32_t img, s
   cp->calc_dims();
   cp->fuse_relus();
   cp->out_node = out_node;
-  if (cp->out_node.empty() && !cp->ops.empty()) cp->out_node = cp->ops.back()->tops.at(0);
+  if (cp->out_node.empty() && !cp->ops.empty()) cp->out_node = cp->ops.back()->tops.back();
+  if (add_bck_ops) cp->add_bck_ops();
   return cp;
 }
 
@@ -337,6 +349,13 @@ void conv_pipe_t::calc_dims() {
         unsup_err("Eltwise operation " + op->eltwise_op);
     } else if (op->type == "LRN") {
       if (op->local_size % 2 == 0 || op->local_size > 11) unsup_err("LRN local_size must be odd and <= 11");
+    } else if (op->type == "SoftmaxWithLoss") {  // tops: the gradient of in, and the loss y:x
+      dims_t const &lb = node_dims.at(op->bots[1]);
+      if (lb != dims_t({{"img", B}, {"y", H}, {"x", W}}))
+        rt_err("layer '" + op->tag + "': label dims " + lb.str() + " are not img:y:x of its input " + in.str());
+      node_dims[op->tops[0]] = in;
+      node_dims[op->tops[1]] = dims_t({{"y", H}, {"x", W}});
+      continue;
     }
     if (op->type != "ReLU" && op->type != "BatchNorm" && op->type != "Scale" && op->type != "LRN" &&
         op->type != "Copy" && op->tops.size() != 1)
@@ -366,6 +385,108 @@ void conv_pipe_t::fuse_relus() {
   }
 }
 
+// The backward ops, by walking the forward ops in reverse (a reverse topological order, so every
+// gradient an op reads has been written): one backward op per forward op, and before the first op that
+// reads the gradient of a blob with several consumers, the Reduce over the partials that exist.
+void conv_pipe_t::add_bck_ops() {
+  auto in_place = [](conv_op_t const &o) { return o.tops == o.bots; };
+  static const std::set<std::string> known = {"Convolution", "InnerProduct", "Pooling", "ReLU", "Dropout",
+                                              "LRN",         "Concat",       "SoftmaxWithLoss"};
+  for (auto const &p : ops)
+    if (!known.count(p->type))
+      unsup_err("add_bck_ops: layer '" + p->tag + "' of type " + p->type + " has no backward op");
+  std::map<std::string, std::vector<conv_op_t const *>> readers;  // out-of-place consumers, in order
+  std::map<std::string, std::string> last_writer;                 // producer, or the last in-place op
+  for (auto const &p : ops) {
+    if (!in_place(*p))
+      for (auto const &b : p->bots) readers[b].push_back(p.get());
+    for (auto const &t : p->tops) last_writer[t] = p->tag;
+  }
+  auto is_source = [&](std::string const &n) { return std::find(inputs.begin(), inputs.end(), n) != inputs.end(); };
+  // the gradient blob consumer c writes for blob x (get_grad_loss_onn, src/conv_util.cc:732-752)
+  auto gl_name = [&](std::string const &x, conv_op_t const &c) {
+    auto const &rs = readers[x];
+    if (rs.size() <= 1 || in_place(c)) return x + "_grad_loss";
+    const size_t ix = std::find(rs.begin(), rs.end(), &c) - rs.begin();
+    auto lw = last_writer.find(x);
+    return x + "_" + (lw == last_writer.end() ? x : lw->second) + "_0_split_" + std::to_string(ix) + "_grad_loss";
+  };
+  std::set<std::string> have, reduced;
+  auto write = [&](std::string const &gl, std::string const &of) {
+    have.insert(gl);
+    node_dims[gl] = node_dims.at(of);
+  };
+  // true once x_grad_loss is written (emits the Reduce a fan-out blob needs)
+  auto out_grad = [&](std::string const &x) {
+    auto const &rs = readers[x];
+    if (rs.size() > 1 && reduced.insert(x).second) {
+      auto r = std::make_shared<conv_op_t>();
+      r->type = "Reduce";
+      r->tag = "reduce_" + x + "_grad_loss";
+      for (conv_op_t const *c : rs)
+        if (have.count(gl_name(x, *c))) r->bots.push_back(gl_name(x, *c));
+      r->tops = {x + "_grad_loss"};
+      if (!r->bots.empty()) {
+        bck_ops.push_back(r);
+        write(r->tops[0], x);
+      }
+    }
+    return have.count(x + "_grad_loss") != 0;
+  };
+  for (auto it = ops.rbegin(); it != ops.rend(); ++it) {
+    conv_op_t const &op = **it;
+    if (op.type == "SoftmaxWithLoss") {  // writes the gradient of its input itself
+      (*it)->tops[0] = gl_name(op.bots[0], op);
+      write(op.tops[0], op.bots[0]);
+      continue;
+    }
+    std::string const &top = op.tops[0];
+    if (readers[top].empty())
+      rt_err("add_bck_ops: top node '" + top + "' (layer '" + op.tag + "') is not produced by a SoftmaxWithLoss op");
+    if (!out_grad(top)) rt_err("add_bck_ops: no gradient reaches blob '" + top + "' (layer '" + op.tag + "')");
+    const std::string og = top + "_grad_loss";
+    auto b = std::make_shared<conv_op_t>(op);
+    b->tag = op.tag + "_bck";
+    b->fused = b->fused_relu = false;
+    std::string const &in = op.bots[0];
+    if (op.type == "Pooling" || op.type == "LRN") {
+      (*it)->emit_aux = true;
+      b->type = op.type == "Pooling" ? "Spreading" : "BckLRN";
+      b->bots = {in, top, og};
+      b->tops = {gl_name(in, op)};
+    } else if (op.type == "ReLU") {
+      b->type = "ZeroIfNonPos";
+      b->bots = {og, top};
+      b->tops = {gl_name(in, op)};
+    } else if (op.type == "Dropout") {
+      b->type = "BckDropout";
+      b->bots = {og};
+      b->tops = {gl_name(in, op)};
+    } else if (op.type == "Concat") {
+      b->type = "Split";
+      b->bots = {og};
+      b->tops.clear();
+      for (auto const &i : op.bots) b->tops.push_back(gl_name(i, op));
+    } else if (op.type == "Convolution" || op.type == "InnerProduct") {
+      b->type = "BckConv";
+      b->bots = {in, op.tag + "_filts", op.tag + "_biases", og};
+      b->tops = {is_source(in) ? std::string() : gl_name(in, op), op.tag + "_filts_grad_loss",
+                 op.tag + "_biases_grad_loss"};
+      dims_t const &d = node_dims.at(in);
+      const bool ip = op.type == "InnerProduct";
+      node_dims[b->tops[1]] = dims_t({{"out_chan", op.out_chans}, {"in_chan", d.dsz("chan")},
+                                      {"y", ip ? d.dsz("y") : op.ky}, {"x", ip ? d.dsz("x") : op.kx}});
+      node_dims[b->tops[2]] = dims_t({{"out_chan", op.out_chans}});
+    } else {
+      unsup_err("add_bck_ops: layer '" + op.tag + "' of type " + op.type + " has no backward op");
+    }
+    for (size_t i = 0; i < b->tops.size() && !(b->type == "BckConv" && i); ++i)
+      if (!b->tops[i].empty()) write(b->tops[i], op.bots[i]);
+    bck_ops.push_back(b);
+  }
+  has_bck = true;
+}
+
 std::string conv_pipe_t::plan_str() const {
   std::ostringstream o;
   for (auto const &in : inputs) o << "input " << in << " " << node_dims.at(in).str() << "\n";
@@ -378,6 +499,14 @@ std::string conv_pipe_t::plan_str() const {
       o << " k=" << op->ky << "x" << op->kx << " s=" << op->sy << "x" << op->sx << " p=" << op->py << "x" << op->px;
     if (op->type == "Pooling") o << (op->avg_pool ? " avg" : " max");
     if (op->fused_relu) o << " +relu";
+    o << "\n";
+  }
+  for (auto const &op : bck_ops) {
+    o << op->type << " " << op->tag << " ";
+    for (size_t i = 0; i < op->bots.size(); ++i) o << (i ? "," : "") << op->bots[i];
+    o << " ->";
+    for (auto const &t : op->tops)
+      if (!t.empty()) o << " " << t << " " << node_dims.at(t).str();
     o << "\n";
   }
   return o.str();
@@ -552,6 +681,91 @@ void conv_pipe_fwd_t::plan_slabs() {
   }
 }
 
+op_base_t conv_pipe_fwd_t::conv_fo(conv_op_t const &op, bool bck) const {
+  // (a BckConv op carries its forward op's geometry and reads the same input blob)
+  dims_t const &in = cp->node_dims.at(op.bots[0]);
+  const bool ip = op.ky == 0;  // InnerProduct: a convolution whose window is the whole input
+  const uint32_t KY = ip ? in.dsz("y") : op.ky, KX = ip ? in.dsz("x") : op.kx;
+  op_base_t fo;
+  fo.type = bck ? "BckConv" : "Convolution";
+  fo.dims_vals["in"] = in;
+  fo.dims_vals["filts"] = dims_t({{"out_chan", op.out_chans}, {"in_chan", in.dsz("chan")}, {"y", KY}, {"x", KX}});
+  fo.dims_vals["kern_sz"] = dims_t({{"y", KY}, {"x", KX}}, "none");
+  fo.dims_vals["stride"] = dims_t({{"y", ip ? 1u : op.sy}, {"x", ip ? 1u : op.sx}}, "none");
+  fo.dims_vals["in_pad"] = dims_t({{"y", ip ? 0u : op.py}, {"x", ip ? 0u : op.px}}, "none");
+  fo.line = op.tag;
+  if (bck) {
+    fo.dims_vals["biases"] = dims_t({{"out_chan", op.out_chans}});
+    fo.dims_vals["out_grad_loss"] = cp->node_dims.at(op.bots[3]);
+  }
+  return fo;
+}
+
+// One call per backward op (conv_pipe_t::add_bck_ops), through the function kinds of hip_compute_t.
+void conv_pipe_fwd_t::gen_bck_op(conv_op_t const &op) {
+  for (auto const &t : op.tops)
+    if (!t.empty() && !declared.count(t)) {
+      rtc->create_var_with_dims(t, cp->node_dims.at(t));
+      declared.insert(t);
+    }
+  op_base_t fo;
+  fo.type = op.type;
+  char buf[64];
+  auto fstr = [&](float v) { snprintf(buf, sizeof(buf), "%.9g", v); return std::string(buf); };
+  if (op.type == "Spreading") {
+    fo.scalars = {{"ky", op.ky}, {"kx", op.kx}, {"sy", op.sy}, {"sx", op.sx},
+                  {"py", op.py}, {"px", op.px}, {"avg", op.avg_pool ? 1u : 0u}};
+    rtc->compile({{"hip_spreading__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_spreading__" + op.tag, op,
+             {{"out", op.bots[1]}, {"out_grad_loss", op.bots[2]}, {"out_in_yx", op.bots[1] + "_in_yx"}, {"in_grad_loss", op.tops[0]}});
+  } else if (op.type == "BckLRN") {
+    fo.scalars = {{"local_size", op.local_size}};
+    fo.str_vals = {{"alpha", fstr(op.alpha)}, {"beta", fstr(op.beta)}, {"k", fstr(op.k)}};
+    rtc->compile({{"hip_bck_lrn__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_bck_lrn__" + op.tag, op,
+             {{"in", op.bots[0]}, {"out", op.bots[1]}, {"out_grad_loss", op.bots[2]},
+              {"out_scale_base", op.bots[1] + "_scale_base"}, {"in_grad_loss", op.tops[0]}});
+  } else if (op.type == "ZeroIfNonPos") {
+    rtc->compile({{"hip_zero_if_non_pos__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_zero_if_non_pos__" + op.tag, op, {{"in", op.bots[0]}, {"cond", op.bots[1]}, {"out", op.tops[0]}});
+  } else if (op.type == "BckDropout") {  // dropout is its own backward: the forward's seed and ratio
+    if (op.tops[0] != op.bots[0]) rt_err("BckDropout '" + op.tag + "' is not in place");
+    fo.str_vals = {{"dropout_ratio", fstr(op.dropout_ratio)}};
+    rtc->compile({{"hip_dropout__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_dropout__" + op.tag, op, {{"inout", op.tops[0]}, {"det_drop_seed", rtc_arg_t::u32(det_drop_seed)}});
+    dropout_cixs.push_back((uint32_t)calls.size() - 1);
+  } else if (op.type == "Split") {
+    uint32_t ic0 = 0;
+    for (size_t i = 0; i < op.tops.size(); ++i) {
+      const uint32_t nc = cp->node_dims.at(op.tops[i]).dsz("chan");
+      op_base_t f2 = fo;
+      f2.scalars = {{"ic0", ic0}, {"oc0", 0}, {"nc", nc}};
+      std::string fn = "hip_copy__" + op.tag + "_" + std::to_string(i);
+      rtc->compile({{fn, "", {}, f2}}, rtc_compile_opts_t());
+      add_call(fn, op, {{"in", op.bots[0]}, {"out", op.tops[i]}});
+      ic0 += nc;
+    }
+  } else if (op.type == "Reduce") {
+    fo.scalars = {{"ins_num", (uint64_t)op.bots.size()}};
+    std::map<std::string, rtc_arg_t> args{{"out", op.tops[0]}};
+    for (size_t i = 0; i < op.bots.size(); ++i) args["ins_" + std::to_string(i)] = op.bots[i];
+    rtc->compile({{"hip_reduce__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_reduce__" + op.tag, op, args);
+  } else if (op.type == "BckConv") {
+    fo = conv_fo(op, true);
+    conv_shape_t s = get_bck_conv_shape(fo);
+    std::map<std::string, rtc_arg_t> args{{"in", op.bots[0]}, {"filts", op.bots[1]}, {"out_grad_loss", op.bots[3]},
+                                          {"filts_grad_loss", op.tops[1]}, {"biases_grad_loss", op.tops[2]}};
+    if (!op.tops[0].empty()) args["in_grad_loss"] = op.tops[0];  // (the first conv: no input gradient)
+    rtc->compile({{"hip_bck_conv__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    // the input and the filter gradient each do the forward's multiply-adds
+    add_call("hip_bck_conv__" + op.tag, op, args,
+             (op.tops[0].empty() ? 2.0 : 4.0) * s.B * s.OH * s.OW * (double)s.OC * s.IC * s.KY * s.KX);
+  } else {
+    unsup_err("conv_pipe_fwd: no executor for backward op type " + op.type);
+  }
+}
+
 void conv_pipe_fwd_t::gen_op(conv_op_t const &op) {
   if (op.fused) return;
   dims_t const &in = cp->node_dims.at(op.bots[0]);
@@ -671,12 +885,31 @@ void conv_pipe_fwd_t::gen_op(conv_op_t const &op) {
     dropout_cixs.push_back((uint32_t)calls.size() - 1);
     return;
   }
+  // emit_aux (add_bck_ops): the var the op's backward op reads, with the dims of out
+  auto aux = [&](std::map<std::string, rtc_arg_t> args, char const *an, char const *suffix) {
+    if (op.emit_aux) {
+      rtc->create_var_with_dims(op.tops[0] + suffix, out);
+      args[an] = op.tops[0] + suffix;
+    }
+    return args;
+  };
   if (op.type == "Pooling") {
     ensure_out(op.tops[0]);
     fo.scalars = {{"ky", op.ky}, {"kx", op.kx}, {"sy", op.sy}, {"sx", op.sx},
                   {"py", op.py}, {"px", op.px}, {"avg", op.avg_pool ? 1u : 0u}};
     rtc->compile({{"hip_pool__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
-    add_call("hip_pool__" + op.tag, op, {{"in", op.bots[0]}, {"out", op.tops[0]}});
+    add_call("hip_pool__" + op.tag, op, aux({{"in", op.bots[0]}, {"out", op.tops[0]}}, "out_in_yx", "_in_yx"));
+    return;
+  }
+  if (op.type == "SoftmaxWithLoss") {  // softmax, gradient and loss, sum over images: one call
+    for (auto const &t : op.tops) ensure_out(t);
+    std::string pv = op.tag + "_prob", lv = op.tops[1] + "_per_pel";
+    rtc->create_var_with_dims(pv, in);
+    rtc->create_var_with_dims(lv, cp->node_dims.at(op.bots[1]));
+    rtc->compile({{"hip_softmax_with_loss__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
+    add_call("hip_softmax_with_loss__" + op.tag, op,
+             {{"in", op.bots[0]}, {"label", op.bots[1]}, {"prob", pv}, {"in_grad_loss", op.tops[0]},
+              {"loss_per_pel", lv}, {"loss", op.tops[1]}});
     return;
   }
   if (op.type == "LRN") {
@@ -689,7 +922,7 @@ void conv_pipe_fwd_t::gen_op(conv_op_t const &op) {
     snprintf(buf, sizeof(buf), "%.9g", op.beta); fo.str_vals["beta"] = buf;
     snprintf(buf, sizeof(buf), "%.9g", op.k); fo.str_vals["k"] = buf;
     rtc->compile({{"hip_lrn__" + op.tag, "", {}, fo}}, rtc_compile_opts_t());
-    add_call("hip_lrn__" + op.tag, op, {{"in", op.bots[0]}, {"out", op.tops[0]}});
+    add_call("hip_lrn__" + op.tag, op, aux({{"in", op.bots[0]}, {"out", op.tops[0]}}, "out_scale_base", "_scale_base"));
     return;
   }
   if (op.type == "Concat" || op.type == "Copy") {
@@ -753,10 +986,14 @@ void conv_pipe_fwd_t::init_with_rtc(p_conv_pipe_t const &cp_, p_rtc_compute_t co
     rtc->create_var_with_dims(in, cp->node_dims.at(in));
     declared.insert(in);
   }
+  // with backward ops every blob keeps a var of its own: the rewrites that hide blobs are off (the
+  // conv + ReLU fusion stays: the fused conv writes the post-ReLU blob ZeroIfNonPos takes as cond)
+  if (cp->has_bck) fold_affines = fuse_residual = concat_in_place = false;
   if (fold_affines) plan_folds();
   if (fuse_residual) plan_resadds();
   if (concat_in_place) plan_slabs();
   for (auto const &op : cp->ops) gen_op(*op);
+  for (auto const &op : cp->bck_ops) gen_bck_op(*op);
   rtc->finish_and_sync();
 }
 

@@ -10,8 +10,8 @@
 //     (bh_time_next_call), so host launch latency is not part of the duration;
 //   * the hot ops are hand-written kernels reached by function name, the way
 //     the reference reaches cuBLAS/cuDNN through its culibs intercept
-//     (src/nvrtc_util.cc:369-372): hip_sgemm, hip_conv, the forward layers and the
-//     gen_data_* test-pattern generators;
+//     (src/nvrtc_util.cc:369-372): hip_sgemm, hip_conv, the forward layers, the
+//     backward ops and the gen_data_* test-pattern generators;
 //   * every other function is CUCL source JIT-compiled through hiprtc for gfx950 with the
 //     CUCL prelude below (the reference prepends its cu_base_decls and compiles with nvrtc,
 //     src/nvrtc_util.cc:150-260) and launched 1-D, blks x tpb, args in arg_names order: a var
@@ -155,7 +155,12 @@ struct hip_compute_t : public rtc_compute_t {
                                                 // BckConv: the combined call (ops-prof), the three calls Boda's
                                                 // conv_pipe_fwd_t emits (src/rtc_fwd.cc:378-400), the bck pack
                                                 "hip_bck_conv", "hip_bck_in", "hip_bck_filts", "hip_bck_biases",
-                                                "hip_bck_xpose_filts"};
+                                                "hip_bck_xpose_filts",
+                                                // the backward ops of the non-conv layers (bh_bckops.hip); BckDropout
+                                                // is hip_dropout, Split is hip_copy
+                                                "hip_spreading", "hip_bck_lrn", "hip_zero_if_non_pos", "hip_reduce",
+                                                "hip_softmax_with_loss", "hip_sm_grad_and_loss",
+                                                "hip_sum_loss_over_imgs"};
     std::string src = cucl_hip_prelude;
     std::vector<std::string> jit_names;
     for (auto const &fi : fis) {
@@ -277,6 +282,16 @@ struct hip_compute_t : public rtc_compute_t {
     auto it = op.str_vals.find("hip_pack_banks");
     return it == op.str_vals.end() ? BH_BANKS_ALL : parse_u32(it->second, "bank mask");
   }
+  // the form of a backward op of a non-conv layer: no cfg = the production kernel, cfg=ref64 = form 1;
+  // these ops have no other configuration, no K splits and no store policy
+  static int bck_op_form(op_base_t const &fop) {
+    if (fop.str_vals.count("hip_splits") || fop.str_vals.count("hip_wt"))
+      unsup_err("op_tune: " + fop.type + " takes no splits or wt");
+    auto cf = fop.str_vals.find("hip_cfg");
+    if (cf == fop.str_vals.end()) return 0;
+    if (cf->second != "ref64") unsup_err("op_tune: no " + fop.type + " configuration named '" + cf->second + "'");
+    return 1;
+  }
   std::string variant_of(int op, uint32_t const *d) {
     char buf[192];
     return bh_variant_name_ctx(ctx, op, d, buf, sizeof buf) == BH_OK ? std::string(buf) : std::string();
@@ -319,9 +334,13 @@ struct hip_compute_t : public rtc_compute_t {
     };
     auto fv = [&](char const *n) -> float {
       auto it = fi.op.str_vals.find(n);
-      if (it == fi.op.str_vals.end()) rt_err(fn + ": op lacks '" + n + "'");
-      return strtof(it->second.c_str(), nullptr);
+      if (it != fi.op.str_vals.end()) return strtof(it->second.c_str(), nullptr);
+      auto is = fi.op.scalars.find(n);  // a legacy op line holds an all-digit value (k=1) as a scalar
+      if (is == fi.op.scalars.end()) rt_err(fn + ": op lacks '" + n + "'");
+      return (float)is->second;
     };
+    // variant name of a backward op: bckop_<name> / ref64_<name>
+    auto bck_variant = [&](int form) { return (form ? "ref64_" : "bckop_") + kind.substr(4); };
     auto nchw = [&](char const *an, uint32_t &B, uint32_t &C, uint32_t &H, uint32_t &W) {
       dims_t const &d = arg_dims(rfc, an);
       B = d.dsz("img"); C = d.dsz("chan"); H = d.dsz("y"); W = d.dsz("x");
@@ -334,15 +353,17 @@ struct hip_compute_t : public rtc_compute_t {
       if (OB != B || OC_ != C || OH != (uint32_t)bh_pool_out_size(H, ky, sy, py) ||
           OW != (uint32_t)bh_pool_out_size(W, kx, sx, px))
         rt_err(fn + ": out dims do not match the pooling geometry");
-      bh_check(bh_pool_fwd_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), nullptr, B, C, H, W, ky, kx, sy, sx, py,
+      // out_in_yx (optional): what the matching Spreading op reads
+      bh_check(bh_pool_fwd_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), arg_ptr(rfc, "out_in_yx", true), B, C, H, W, ky, kx, sy, sx, py,
                                 px, (int)sc("avg")),
                fn);
     } else if (kind == "hip_lrn") {
       uint32_t B, C, H, W;
       nchw("in", B, C, H, W);
       if (arg_dims(rfc, "out") != arg_dims(rfc, "in")) rt_err(fn + ": in / out dims differ");
-      bh_check(bh_lrn_fwd_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), nullptr, B, C, H, W, sc("local_size"),
-                               fv("alpha"), fv("beta"), fv("k")),
+      // out_scale_base (optional): what the matching BckLRN op reads
+      bh_check(bh_lrn_fwd_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), arg_ptr(rfc, "out_scale_base", true), B, C,
+                               H, W, sc("local_size"), fv("alpha"), fv("beta"), fv("k")),
                fn);
     } else if (kind == "hip_relu") {
       bh_check(bh_relu_inplace(ctx, arg_ptr(rfc, "x"), arg_dims(rfc, "x").elems()), fn);
@@ -350,6 +371,9 @@ struct hip_compute_t : public rtc_compute_t {
       // det_drop_seed is a by-value CALL argument (set_det_drop_seed rewrites it per forward)
       auto sd = rfc.arg_map.find("det_drop_seed");
       if (sd == rfc.arg_map.end() || !sd->second.has_v) rt_err(fn + ": call lacks the det_drop_seed value");
+      // BckDropout is the same call with the forward's seed and ratio; one exact multiply per element, so
+      // the one kernel is its own ref64 form
+      if (fi.op.type == "BckDropout") ev.variant = bck_variant(bck_op_form(fi.op));
       bh_check(bh_dropout_inplace(ctx, arg_ptr(rfc, "inout"), arg_dims(rfc, "inout").elems(), fv("dropout_ratio"),
                                   (uint32_t)sd->second.v),
                fn);
@@ -360,6 +384,79 @@ struct hip_compute_t : public rtc_compute_t {
       const uint32_t ic0 = sc("ic0"), oc0 = sc("oc0"), nc = sc("nc");
       if (B != OB || H != OH || W != OW || ic0 + nc > C || oc0 + nc > OC_) rt_err(fn + ": channel slab out of range");
       bh_check(bh_chan_copy(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), B, H * W, C, ic0, OC_, oc0, nc), fn);
+    } else if (kind == "hip_spreading") {  // test/rtc/spreading.cucl: out_grad_loss, out_in_yx, in_grad_loss
+      uint32_t B, C, H, W, OB, OC_, OH, OW;
+      nchw("in_grad_loss", B, C, H, W);
+      nchw("out_grad_loss", OB, OC_, OH, OW);
+      const uint32_t ky = sc("ky"), kx = sc("kx"), sy = sc("sy"), sx = sc("sx"), py = sc("py"), px = sc("px");
+      const int avg = (int)sc("avg"), form = bck_op_form(fi.op);
+      if (OB != B || OC_ != C || OH != (uint32_t)bh_pool_out_size(H, ky, sy, py) ||
+          OW != (uint32_t)bh_pool_out_size(W, kx, sx, px))
+        rt_err(fn + ": out_grad_loss dims do not match the pooling geometry");
+      if (!avg && arg_dims(rfc, "out_in_yx") != arg_dims(rfc, "out_grad_loss")) rt_err(fn + ": out_in_yx dims");
+      ev.variant = bck_variant(form);
+      bh_check(bh_spreading_nchw(ctx, arg_ptr(rfc, "out_grad_loss"), arg_ptr(rfc, "out_in_yx", avg != 0),
+                                 arg_ptr(rfc, "in_grad_loss"), B, C, H, W, ky, kx, sy, sx, py, px, avg, form),
+               fn);
+    } else if (kind == "hip_bck_lrn") {  // test/rtc/bck_lrn.cucl
+      uint32_t B, C, H, W;
+      nchw("in", B, C, H, W);
+      for (char const *an : {"out", "out_scale_base", "out_grad_loss", "in_grad_loss"})
+        if (arg_dims(rfc, an) != arg_dims(rfc, "in")) rt_err(fn + ": " + an + " / in dims differ");
+      const int form = bck_op_form(fi.op);
+      ev.variant = bck_variant(form);
+      bh_check(bh_lrn_bck_nchw(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "out"), arg_ptr(rfc, "out_scale_base"),
+                               arg_ptr(rfc, "out_grad_loss"), arg_ptr(rfc, "in_grad_loss"), B, C, H, W,
+                               sc("local_size"), fv("alpha"), fv("beta"), fv("k"), form),
+               fn);
+    } else if (kind == "hip_zero_if_non_pos") {  // test/rtc/ZeroIfNonPos.cucl: in, cond, out (out may be in)
+      dims_t const &d = arg_dims(rfc, "out");
+      if (arg_dims(rfc, "in") != d || arg_dims(rfc, "cond") != d) rt_err(fn + ": in / cond / out dims differ");
+      const int form = bck_op_form(fi.op);
+      ev.variant = bck_variant(form);
+      bh_check(bh_zero_if_non_pos(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "cond"), arg_ptr(rfc, "out"), d.elems(), form),
+               fn);
+    } else if (kind == "hip_reduce") {  // test/rtc/reduce.cucl: ins_0 .. ins_<ins_num - 1>, out
+      dims_t const &d = arg_dims(rfc, "out");
+      const uint32_t n_ins = sc("ins_num");
+      std::vector<const float *> ins;
+      for (uint32_t i = 0; i < n_ins; ++i) {
+        const std::string an = "ins_" + std::to_string(i);
+        if (arg_dims(rfc, an) != d) rt_err(fn + ": " + an + " / out dims differ");
+        ins.push_back(arg_ptr(rfc, an));
+      }
+      const int form = bck_op_form(fi.op);
+      ev.variant = bck_variant(form);
+      bh_check(bh_reduce_sum(ctx, ins.data(), n_ins, arg_ptr(rfc, "out"), d.elems(), form), fn);
+    } else if (kind == "hip_softmax_with_loss" || kind == "hip_sm_grad_and_loss") {
+      // test/rtc/sm_grad_and_loss.cucl: prob, label, in_grad_loss, loss_per_pel; the whole op adds in and loss
+      uint32_t B, C, H, W;
+      nchw("prob", B, C, H, W);
+      dims_t const &lb = arg_dims(rfc, "label");
+      if (arg_dims(rfc, "in_grad_loss") != arg_dims(rfc, "prob")) rt_err(fn + ": in_grad_loss / prob dims differ");
+      if (lb.elems() != (uint64_t)B * H * W || arg_dims(rfc, "loss_per_pel") != lb)
+        rt_err(fn + ": label / loss_per_pel are not img x y x x of prob");
+      const int form = bck_op_form(fi.op);
+      ev.variant = bck_variant(form);
+      if (kind == "hip_sm_grad_and_loss") {
+        bh_check(bh_sm_grad_and_loss(ctx, arg_ptr(rfc, "prob"), arg_ptr(rfc, "label"), arg_ptr(rfc, "in_grad_loss"),
+                                     arg_ptr(rfc, "loss_per_pel"), B, C, H, W, form),
+                 fn);
+      } else {
+        if (arg_dims(rfc, "in") != arg_dims(rfc, "prob")) rt_err(fn + ": in / prob dims differ");
+        if (arg_dims(rfc, "loss").elems() != (uint64_t)H * W) rt_err(fn + ": loss is not y x x of in");
+        bh_check(bh_softmax_with_loss(ctx, arg_ptr(rfc, "in"), arg_ptr(rfc, "label"), arg_ptr(rfc, "prob"),
+                                      arg_ptr(rfc, "in_grad_loss"), arg_ptr(rfc, "loss_per_pel"), arg_ptr(rfc, "loss"),
+                                      B, C, H, W, form),
+                 fn);
+      }
+    } else if (kind == "hip_sum_loss_over_imgs") {  // test/rtc/sum_loss_over_imgs.cucl: loss_per_pel, loss
+      dims_t const &lp = arg_dims(rfc, "loss_per_pel");
+      const uint32_t B = lp.dsz("img"), HW = (uint32_t)(lp.elems() / B);
+      if (arg_dims(rfc, "loss").elems() != HW) rt_err(fn + ": loss is not y x x of loss_per_pel");
+      const int form = bck_op_form(fi.op);
+      ev.variant = bck_variant(form);
+      bh_check(bh_sum_loss_over_imgs(ctx, arg_ptr(rfc, "loss_per_pel"), arg_ptr(rfc, "loss"), B, HW, form), fn);
     } else if (kind == "hip_affine") {
       uint32_t B, C, H, W;
       nchw("in", B, C, H, W);
@@ -460,8 +557,9 @@ struct hip_compute_t : public rtc_compute_t {
       bh_check(bh_conv_bck_filts_pack(ctx, arg_ptr(rfc, "filts"), arg_ptr(rfc, "filts_xp"), s.OC, s.IC, s.KY, s.KX),
                "hip_bck_xpose_filts");
     } else {  // gen_data_<type>_<arg>
-      std::string an = fn.substr(fn.rfind('_') + 1);
-      if (fn == "gen_data_BckConv_out_grad_loss") an = "out_grad_loss";
+      // the var name: what follows gen_data_<op type>_
+      const std::string pre = "gen_data_" + fi.op.type + "_";
+      std::string an = fn.rfind(pre, 0) == 0 ? fn.substr(pre.size()) : fn.substr(fn.rfind('_') + 1);
       uint32_t mode = (uint32_t)arg_val(rfc, "mode", 5);
       float vi = (float)arg_val(rfc, "vi", 0.0);
       dims_t const &d = arg_dims(rfc, an);
@@ -476,9 +574,21 @@ struct hip_compute_t : public rtc_compute_t {
       else if (fn == "gen_data_BckConv_filts") kind = BH_GEN_CONV_FILTS;
       else if (fn == "gen_data_BckConv_biases") kind = BH_GEN_CONV_BIASES;
       else if (fn == "gen_data_BckConv_out_grad_loss") kind = BH_GEN_BCK_OUT_GRAD;
-      else unsup_err("no gen_data generator '" + fn + "'");
+      else if (is_bck_op_type(fi.op.type) || fi.op.type == "Split") {
+        // the backward ops of the non-conv layers: by var. Activations use the Convolution in generator,
+        // gradients out_grad_loss's, cond its own seed; label: integers in [0, C)
+        if (an == "out_grad_loss") kind = BH_GEN_BCK_OUT_GRAD;
+        else if (an == "cond") kind = BH_GEN_COND;
+        else if (an == "label") kind = BH_GEN_LABEL;
+        else if (an == "in" || an == "inout" || an.rfind("ins_", 0) == 0) kind = BH_GEN_CONV_IN;
+        else unsup_err("no gen_data generator '" + fn + "'");
+      } else unsup_err("no gen_data generator '" + fn + "'");
       if (d.d.size() > 4) rt_err("gen_data: too many dims");
       for (size_t i = 0; i < d.d.size(); ++i) dd[i] = d.d[i].sz;
+      if (kind == BH_GEN_LABEL) {  // img:y:x and the class count
+        if (d.d.size() != 3) rt_err(fn + ": label is not img x y x x");
+        dd[3] = fi.op.get_dims("in").dsz("chan");
+      }
       bh_check(bh_gen_data(ctx, kind, arg_ptr(rfc, an), dd, mode, vi), fn);
     }
     calls.push_back(ev);

@@ -164,9 +164,114 @@ sgemm_shape_t get_sgemm_shape(op_base_t const &op) {
   return s;
 }
 
+uint32_t pool_in_sz_to_out_sz(uint32_t in, uint32_t pad, uint32_t k, uint32_t stride) {
+  uint32_t p = in + 2 * pad;
+  if (p < k) return 1;
+  return (p - k + stride - 1) / stride + 1;
+}
+
+bool is_bck_op_type(std::string const &t) {
+  return t == "Spreading" || t == "BckLRN" || t == "ZeroIfNonPos" || t == "BckDropout" || t == "Reduce" ||
+         t == "SoftmaxWithLoss";
+}
+
+namespace {
+struct nchw_t {
+  uint32_t v[4];
+  bool operator!=(nchw_t const &o) const { return !std::equal(v, v + 4, o.v); }
+};
+nchw_t get_nchw(op_base_t const &op, std::string const &n) {
+  dims_t const &d = op.get_dims(n);
+  char const *names[4] = {"img", "chan", "y", "x"};
+  if (d.d.size() != 4) rt_err(n + " is not img x chan x y x x: " + op.line);
+  nchw_t r;
+  for (int i = 0; i < 4; ++i) {
+    if (d.d[i].name != names[i]) rt_err(n + " is not img x chan x y x x: " + op.line);
+    r.v[i] = d.d[i].sz;
+  }
+  return r;
+}
+void check_same(op_base_t const &op, std::vector<std::string> const &names, nchw_t const &want) {
+  for (auto const &n : names)
+    if (get_nchw(op, n) != want) rt_err(n + " dims differ from the op's geometry: " + op.line);
+}
+uint32_t scalar_or(op_base_t const &op, std::string const &n, uint32_t dflt) {
+  auto it = op.scalars.find(n);
+  return it == op.scalars.end() ? dflt : (uint32_t)it->second;
+}
+}  // namespace
+
+bck_op_shape_t get_bck_op_shape(op_base_t const &op) {
+  bck_op_shape_t s;
+  std::string const &t = op.type;
+  if (!is_bck_op_type(t)) rt_err("not a backward op of a non-conv layer: " + t);
+  nchw_t d = get_nchw(op, t == "Spreading" || t == "BckLRN" || t == "SoftmaxWithLoss" ? "in" : "out");
+  s.B = d.v[0]; s.C = d.v[1]; s.H = d.v[2]; s.W = d.v[3];
+  if (t == "Spreading") {
+    dims_t const &st = op.get_dims("stride"), &pd = op.get_dims("in_pad");
+    s.KY = s.H; s.KX = s.W;  // no kern_sz: global pooling
+    if (op.has_dims("kern_sz")) { s.KY = op.get_dims("kern_sz").dsz("y"); s.KX = op.get_dims("kern_sz").dsz("x"); }
+    s.sy = st.dsz("y"); s.sx = st.dsz("x"); s.py = pd.dsz("y"); s.px = pd.dsz("x");
+    s.avg = scalar_or(op, "avg_pool", 0);
+    if (!s.KY || !s.KX || !s.sy || !s.sx) rt_err("zero kern_sz or stride: " + op.line);
+    s.OH = pool_in_sz_to_out_sz(s.H, s.py, s.KY, s.sy);
+    s.OW = pool_in_sz_to_out_sz(s.W, s.px, s.KX, s.sx);
+    check_same(op, {"in_grad_loss"}, d);
+    nchw_t o{{s.B, s.C, s.OH, s.OW}};
+    check_same(op, {"out_grad_loss"}, o);
+    if (op.has_dims("out")) check_same(op, {"out"}, o);
+  } else if (t == "BckLRN") {
+    check_same(op, {"out", "out_grad_loss", "in_grad_loss"}, d);
+    if (!op.scalars.count("local_size")) rt_err("BckLRN op without local_size: " + op.line);
+    s.local_size = scalar_or(op, "local_size", 0);
+  } else if (t == "SoftmaxWithLoss") {
+    check_same(op, {"in_grad_loss"}, d);
+    dims_t want_label({{"img", s.B}, {"y", s.H}, {"x", s.W}}), want_loss({{"y", s.H}, {"x", s.W}});
+    if (op.get_dims("label").str() != want_label.str()) rt_err("label dims inconsistent with in: " + op.line);
+    if (op.get_dims("loss").str() != want_loss.str()) rt_err("loss dims inconsistent with in: " + op.line);
+  } else if (t == "Reduce") {
+    std::vector<std::string> names{"out"};
+    while (op.has_dims("ins_" + std::to_string(s.n_ins))) names.push_back("ins_" + std::to_string(s.n_ins++));
+    if (!s.n_ins || op.dims_vals.size() != s.n_ins + 1) rt_err("Reduce op needs ins_0 .. ins_n-1 and out: " + op.line);
+    check_same(op, names, d);
+  } else {
+    std::vector<std::string> names{"in", "out"};
+    if (t == "ZeroIfNonPos") names.push_back("cond");
+    if (op.dims_vals.size() != names.size()) rt_err(t + " op lists other tensors than its own: " + op.line);
+    check_same(op, names, d);
+  }
+  return s;
+}
+
 op_work_t op_work(op_base_t const &op) {
   op_work_t w;
-  if (op.type == "Convolution") {
+  if (is_bck_op_type(op.type)) {
+    // bytes = 4 x the elements of every tensor the definition reads or writes (boda_hip/ops.py BckOpShape
+    // states the same model)
+    bck_op_shape_t s = get_bck_op_shape(op);
+    double N = s.N(), P = (double)s.B * s.H * s.W;
+    if (op.type == "Spreading") {  // flops: the windows that can cover a pixel
+      w.flops = N * ((s.KY + s.sy - 1) / s.sy) * ((s.KX + s.sx - 1) / s.sx);
+      w.bytes = 4.0 * ((s.avg ? 1.0 : 2.0) * s.B * s.C * s.OH * s.OW + N);
+    } else if (op.type == "BckLRN") {
+      w.flops = N * (s.local_size + 8);
+      w.bytes = 4.0 * 5 * N;
+    } else if (op.type == "SoftmaxWithLoss") {
+      w.flops = 3 * N;
+      w.bytes = 4.0 * (3 * N + 2 * P + (double)s.H * s.W);
+    } else if (op.type == "Reduce") {
+      w.flops = s.n_ins * N;
+      w.bytes = 4.0 * (s.n_ins + 1) * N;
+    } else if (op.type == "BckDropout") {
+      w.flops = N;
+      w.bytes = 4.0 * 2 * N;
+    } else {  // ZeroIfNonPos
+      w.flops = 0;
+      w.bytes = 4.0 * 3 * N;
+    }
+  } else if (op.type == "Split") {  // in read once, the outs (as many elements) written
+    w.bytes = 4.0 * 2 * op.get_dims("in").elems();
+  } else if (op.type == "Convolution") {
     conv_shape_t s = get_conv_shape(op);
     double M = (double)s.B * s.OH * s.OW, K = (double)s.IC * s.KY * s.KX, N = s.OC;
     w.flops = 2 * M * N * K;
@@ -217,6 +322,50 @@ void add_hip_annotations(op_base_t &op) {
   if (op.type == "sgemm") {
     get_sgemm_shape(op);
     op.func_name = "hip_sgemm";
+    return;
+  }
+  if (is_bck_op_type(op.type)) {
+    // the vars of the .cucl definitions (test/rtc/{spreading,bck_lrn,ZeroIfNonPos,reduce,dropout}.cucl and
+    // the three calls of SoftmaxWithLoss), those the forward op makes (out_in_yx, out_scale_base) included
+    bck_op_shape_t s = get_bck_op_shape(op);
+    const dims_t full({{"img", s.B}, {"chan", s.C}, {"y", s.H}, {"x", s.W}});
+    if (op.type == "Spreading") {
+      op.func_name = "hip_spreading";
+      const dims_t o({{"img", s.B}, {"chan", s.C}, {"y", s.OH}, {"x", s.OW}});
+      for (char const *n : {"out", "out_grad_loss", "out_in_yx"}) op.dims_vals[n] = o;
+      // hip_pool's geometry names, so the op also describes the forward call that makes out_in_yx
+      op.scalars["ky"] = s.KY; op.scalars["kx"] = s.KX; op.scalars["sy"] = s.sy; op.scalars["sx"] = s.sx;
+      op.scalars["py"] = s.py; op.scalars["px"] = s.px; op.scalars["avg"] = s.avg;
+    } else if (op.type == "BckLRN") {
+      op.func_name = "hip_bck_lrn";
+      op.dims_vals["out_scale_base"] = full;
+    } else if (op.type == "ZeroIfNonPos") {
+      op.func_name = "hip_zero_if_non_pos";
+    } else if (op.type == "BckDropout") {  // in place, and its own backward
+      op.func_name = "hip_dropout";
+      op.dims_vals["inout"] = full;
+    } else if (op.type == "Reduce") {
+      op.func_name = "hip_reduce";
+      op.scalars["ins_num"] = s.n_ins;
+    } else {
+      op.func_name = "hip_softmax_with_loss";
+      op.dims_vals["prob"] = full;
+      op.dims_vals["loss_per_pel"] = op.get_dims("label");
+    }
+    return;
+  }
+  if (op.type == "Split") {  // one hip_copy per outs_<i>, its channels taken in order from in
+    dims_t const &in = op.get_dims("in");
+    uint32_t n = 0, chans = 0;
+    for (; op.has_dims("outs_" + std::to_string(n)); ++n) {
+      dims_t const &o = op.get_dims("outs_" + std::to_string(n));
+      if (o.dsz("img") != in.dsz("img") || o.dsz("y") != in.dsz("y") || o.dsz("x") != in.dsz("x"))
+        rt_err("Split: outs_" + std::to_string(n) + " differs from in outside chan: " + op.line);
+      chans += o.dsz("chan");
+    }
+    if (!n || chans != in.dsz("chan")) rt_err("Split: the outs' channels do not add up to in's: " + op.line);
+    op.func_name = "hip_copy";
+    op.scalars["outs_num"] = n;
     return;
   }
   unsup_err("hip backend: no kernel for op type '" + op.type + "'");

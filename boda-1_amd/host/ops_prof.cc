@@ -116,21 +116,40 @@ std::vector<std::string> read_lines(std::string const &fn) {
   return lines;
 }
 
-std::vector<std::string> arg_vars(op_base_t const &op) {
-  if (op.type == "Convolution") return {"in", "filts", "biases", "out"};
-  if (op.type == "BckConv")
-    return {"in", "filts", "biases", "out_grad_loss", "in_grad_loss", "filts_grad_loss", "biases_grad_loss"};
-  return {"a", "b", "c"};
-}
-std::vector<std::string> in_vars(op_base_t const &op) {
-  if (op.type == "Convolution") return {"in", "filts", "biases"};
-  if (op.type == "BckConv") return {"in", "filts", "biases", "out_grad_loss"};
-  return {"a", "b"};
-}
-std::vector<std::string> out_vars(op_base_t const &op) {
-  if (op.type == "Convolution") return {"out"};
-  if (op.type == "BckConv") return {"in_grad_loss", "filts_grad_loss", "biases_grad_loss"};
-  return {"c"};
+// the vars of an op's profiling run: args are those of the timed call, extra those only the untimed
+// forward pre-call takes, ins are filled by gen_data_<type>_<var>, outs are compared and digested
+struct prof_vars_t {
+  std::vector<std::string> args, extra, ins, outs;
+};
+prof_vars_t prof_vars(op_base_t const &op) {
+  std::string const &t = op.type;
+  if (t == "Convolution") return {{"in", "filts", "biases", "out"}, {}, {"in", "filts", "biases"}, {"out"}};
+  if (t == "BckConv")
+    return {{"in", "filts", "biases", "out_grad_loss", "in_grad_loss", "filts_grad_loss", "biases_grad_loss"},
+            {},
+            {"in", "filts", "biases", "out_grad_loss"},
+            {"in_grad_loss", "filts_grad_loss", "biases_grad_loss"}};
+  // out and out_in_yx come from hip_pool on a generated in, out and out_scale_base from hip_lrn
+  if (t == "Spreading")
+    return {{"out", "out_grad_loss", "out_in_yx", "in_grad_loss"}, {"in"}, {"in", "out_grad_loss"}, {"in_grad_loss"}};
+  if (t == "BckLRN")
+    return {{"in", "out", "out_grad_loss", "out_scale_base", "in_grad_loss"}, {}, {"in", "out_grad_loss"}, {"in_grad_loss"}};
+  if (t == "ZeroIfNonPos") return {{"in", "cond", "out"}, {}, {"in", "cond"}, {"out"}};
+  if (t == "BckDropout") return {{"inout"}, {}, {"inout"}, {"inout"}};
+  if (t == "SoftmaxWithLoss")
+    return {{"in", "label", "prob", "in_grad_loss", "loss_per_pel", "loss"}, {}, {"in", "label"}, {"in_grad_loss", "loss"}};
+  if (t == "Reduce" || t == "Split") {
+    const bool red = t == "Reduce";
+    prof_vars_t v;
+    std::vector<std::string> &many = red ? v.ins : v.outs;
+    for (uint32_t i = 0; op.has_dims((red ? "ins_" : "outs_") + std::to_string(i)); ++i)
+      many.push_back((red ? "ins_" : "outs_") + std::to_string(i));
+    (red ? v.outs : v.ins).push_back(red ? "out" : "in");
+    v.args = v.ins;
+    v.args.insert(v.args.end(), v.outs.begin(), v.outs.end());
+    return v;
+  }
+  return {{"a", "b", "c"}, {}, {"a", "b"}, {"c"}};
 }
 
 }  // namespace
@@ -160,7 +179,14 @@ int main(int argc, char **argv) {
       }
       for (auto const &op : read_op_list(o.get("dump-ops"), &skipped, types)) {
         op_work_t w = op_work(op);
-        if (op.type == "BckConv") {
+        if (is_bck_op_type(op.type)) {  // B C H W, then what the type adds (ops.py BckOpShape.as_dims)
+          bck_op_shape_t s = get_bck_op_shape(op);
+          std::printf("%s %u %u %u %u", op.type.c_str(), s.B, s.C, s.H, s.W);
+          if (op.type == "Spreading") std::printf(" %u %u %u %u %u %u %u", s.KY, s.KX, s.sy, s.sx, s.py, s.px, s.avg);
+          else if (op.type == "BckLRN") std::printf(" %u", s.local_size);
+          else if (op.type == "Reduce") std::printf(" %u", s.n_ins);
+          std::printf(" %.0f %.0f\n", w.flops, w.bytes);
+        } else if (op.type == "BckConv") {
           conv_shape_t s = get_bck_conv_shape(op);
           std::printf("BckConv %u %u %u %u %u %u %u %u %u %u %u %.0f %.0f\n", s.B, s.IC, s.H, s.W, s.OC, s.KY, s.KX,
                       s.sy, s.sx, s.py, s.px, w.flops, w.bytes);
@@ -189,7 +215,7 @@ int main(int argc, char **argv) {
                    "  [--func-mrd-toler='(variant-or-word=toler,...)'] [--wino-mrd-toler=2e-3] [--max-err=10]\n"
                    "  [--gen-data-mode=5] [--run-iter=1] [--mrd-toler=2e-4] [--device=0] [--write-runs=0]\n"
                    "  [--write-kg-digest=1] [--live-mrd-toler=0]\n"
-                   "  [--skip-ops=0] [--shard=k/n] | --selftest-wisdom=F | --dump-ops=F [--types=T,...] | --list-shard=k/n --ops-fn=F\n";
+                   "  [--skip-ops=0] [--shard=k/n] [--types=T,...] | --selftest-wisdom=F | --dump-ops=F [--types=T,...] | --list-shard=k/n --ops-fn=F\n";
       return 2;
     }
     const uint32_t mode = parse_u32(o.get("gen-data-mode", "5"), "--gen-data-mode");
@@ -266,6 +292,13 @@ int main(int argc, char **argv) {
     std::vector<bool> mine(lines.size(), true);
     if (!o.get("shard").empty()) mine = lpt_mine(lines, o.get("shard"));
 
+    // --types=T1,T2: only the lines of these op types (default: every line)
+    std::vector<std::string> run_types;
+    for (std::string t = o.get("types"); !t.empty();) {
+      size_t c = t.find(',');
+      run_types.push_back(t.substr(0, c));
+      t = c == std::string::npos ? "" : t.substr(c + 1);
+    }
     p_rtc_compute_t rtc = make_hip_compute(parse_i32(o.get("device", "0"), "--device"));
     rtc->init();
     const std::string plat = rtc->get_plat_tag();
@@ -285,6 +318,7 @@ int main(int argc, char **argv) {
       op_base_t op0 = parse_op_line(lines[ix]);
       if (have_wi && !same_op(parse_op_line(wi.op_line), op0)) rt_err("op mismatch between input wisdom and ops-list at op " + std::to_string(ix));
       if (!mine[ix]) continue;
+      if (!run_types.empty() && std::find(run_types.begin(), run_types.end(), op0.type) == run_types.end()) continue;
       op_wisdom_t wo;
       wo.op_line = lines[ix];
       bool op_seen_errs = false;  // the op is printed once, before its first error (on_op_err)
@@ -298,24 +332,59 @@ int main(int argc, char **argv) {
         std::ostringstream err, err_extra;
         std::map<std::string, p_nda_t> outs;
         std::string variant;
+        const prof_vars_t pv = prof_vars(op0);
+        std::vector<std::string> all_vars = pv.args;
+        all_vars.insert(all_vars.end(), pv.extra.begin(), pv.extra.end());
         try {
           add_hip_annotations(op, tune);
           std::vector<rtc_func_info_t> fis{{op.func_name, "", {}, op}};
-          for (auto const &vn : in_vars(op)) fis.push_back({"gen_data_" + op.type + "_" + vn, "", {}, op});
+          for (auto const &vn : pv.ins) fis.push_back({"gen_data_" + op.type + "_" + vn, "", {}, op});
           rtc->compile(fis, rtc_compile_opts_t());
-          for (auto const &vn : arg_vars(op)) rtc->create_var_with_dims(vn, op.get_dims(vn));
-          for (auto const &vn : in_vars(op)) {
+          for (auto const &vn : all_vars) rtc->create_var_with_dims(vn, op.get_dims(vn));
+          for (size_t i = 0; i < pv.ins.size(); ++i) {
+            std::string const &vn = pv.ins[i];
             rtc_func_call_t g;
             g.rtc_func_name = "gen_data_" + op.type + "_" + vn;
             g.arg_map[vn] = vn;
             g.arg_map["mode"] = rtc_arg_t::val(mode);
-            g.arg_map["vi"] = rtc_arg_t::val(0.0);
+            // Reduce's ins_<i> share a generator: each gets an offset of its own
+            g.arg_map["vi"] = rtc_arg_t::val(op.type == "Reduce" ? 0.25 * i : 0.0);
             rtc->run(g);
           }
-          rtc_func_call_t c;
+          // the timed calls: one, but for Split one hip_copy per outs_<i>
+          std::vector<rtc_func_call_t> cs(1);
+          rtc_func_call_t &c = cs[0];
           c.rtc_func_name = op.func_name;
-          for (auto const &vn : arg_vars(op)) c.arg_map[vn] = vn;
-          if (op.type == "Convolution") {
+          for (auto const &vn : pv.args) c.arg_map[vn] = vn;
+          if (op.type == "Spreading" || op.type == "BckLRN") {
+            // the forward op on the generated in, untimed like xpose_filts: it makes the out and the
+            // out_in_yx / out_scale_base the backward op reads, so they are consistent
+            const bool pool = op.type == "Spreading";
+            rtc_func_call_t f;
+            f.rtc_func_name = pool ? "hip_pool" : "hip_lrn";
+            rtc->compile({{f.rtc_func_name, "", {}, op}}, rtc_compile_opts_t());
+            for (char const *vn : {"in", "out"}) f.arg_map[vn] = vn;
+            f.arg_map[pool ? "out_in_yx" : "out_scale_base"] = pool ? "out_in_yx" : "out_scale_base";
+            rtc->run(f);
+          } else if (op.type == "BckDropout") {
+            c.arg_map["det_drop_seed"] = rtc_arg_t::u32(1);
+          } else if (op.type == "Split") {
+            cs.clear();
+            uint32_t ic0 = 0;
+            for (auto const &vn : pv.outs) {
+              op_base_t co = op;
+              co.scalars["ic0"] = ic0;
+              co.scalars["oc0"] = 0;
+              co.scalars["nc"] = op.get_dims(vn).dsz("chan");
+              ic0 += op.get_dims(vn).dsz("chan");
+              rtc_func_call_t cc;
+              cc.rtc_func_name = "hip_copy__" + vn;
+              rtc->compile({{cc.rtc_func_name, "", {}, co}}, rtc_compile_opts_t());
+              cc.arg_map["in"] = "in";
+              cc.arg_map["out"] = vn;
+              cs.push_back(cc);
+            }
+          } else if (op.type == "Convolution") {
             // layout transform of the filters before the timed calls, as the reference's
             // xpose_filts (src/rtc_prof.cc:93-99; untimed)
             conv_shape_t s = get_conv_shape(op);
@@ -341,18 +410,26 @@ int main(int argc, char **argv) {
             rtc->run(x);
             c.arg_map["filts_xp"] = "filts_xp";
           }
-          uint32_t call_id = 0;
-          for (uint32_t r = 0; r < run_iter; ++r) call_id = rtc->run(c);
+          // the time is that of the last iteration: one dispatch's own events for every type but Split,
+          // whose copies make a span from the first copy's begin to the last one's end, gaps included --
+          // good for a sum over ops, not comparable with the single-dispatch times; the variant printed is
+          // the last call's
+          uint32_t first_id = 0, call_id = 0;
+          for (uint32_t r = 0; r < run_iter; ++r)
+            for (size_t i = 0; i < cs.size(); ++i) {
+              call_id = rtc->run(cs[i]);
+              if (!i) first_id = call_id;
+            }
           rtc->finish_and_sync();
-          run.rt_secs = rtc->get_dur(call_id, call_id) / 1000.0;
+          run.rt_secs = rtc->get_dur(first_id, call_id) / 1000.0;
           variant = rtc->get_call_variant(call_id);
-          for (auto const &vn : out_vars(op)) outs[vn] = rtc->create_nda_from_var(vn);
+          for (auto const &vn : pv.outs) outs[vn] = rtc->create_nda_from_var(vn);
           run.op_line = op.line;
         } catch (unsup_exception const &e) {
           err << "profile call failure: " << e.what();
           ++n_unsup;  // recorded, not a MAD failure (src/rtc_prof.cc:287-296, :368-369)
         }
-        for (auto const &vn : arg_vars(op))
+        for (auto const &vn : all_vars)
           if (op.has_dims(vn)) {
             try {
               rtc->release_var(vn);
@@ -415,7 +492,7 @@ int main(int argc, char **argv) {
             }
             if (dstat == "FAIL") ++num_mad_fail;
           }
-          op_work_t w = op_work(op);
+          op_work_t w = op_work(op0);  // (the annotated op lists vars of its own)
           agg_t &g = agg[tag];
           g.flops += w.flops;
           g.secs += run.rt_secs;

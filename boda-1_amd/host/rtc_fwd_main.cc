@@ -8,7 +8,14 @@
 //   boda_hip_rtc_fwd --net nets/alexnet/train_val.prototxt [--img 20] [--out-node pool5]
 //                    [--iters 5] [--plan | --plan-json | --plan-exec] [--save DIR] [--save-blobs DIR
 //                    [--blob-sample N]] [--device 0] [--no-pack] [--no-fold] [--no-inplace-concat]
-//                    [--no-resadd] [--graph R] [--det-dropout SEED] [--mode-args "(k=v,...)"]
+//                    [--no-resadd] [--graph R] [--det-dropout SEED] [--add-bck-ops] [--mode-args "(k=v,...)"]
+//
+// --add-bck-ops reads the TRAIN-phase net with its SoftmaxWithLoss ops and appends the backward ops
+// (conv_pipe_t::add_bck_ops): --plan / --plan-json list them after the forward ones, a run computes the
+// loss and every <blob>_grad_loss, <layer>_filts_grad_loss and <layer>_biases_grad_loss (--save-blobs
+// writes them like any blob; --graph times the forward and backward run as one graph). Dropout layers run
+// with the mask of --det-dropout SEED (default 0). The label input is synthetic: label[i] =
+// floor((det_hash_rand(i + 90417263) + 5) / 10 * C), at most C - 1, C the classes of the first loss.
 //
 // --plan / --plan-json print the net plan without touching a GPU (host logic tests); --plan-exec
 // the executor's BatchNorm/Scale folds and in-place Concat slabs. Mode options (nia): --no-pack
@@ -86,6 +93,17 @@ std::string plan_json(conv_pipe_t const &cp) {
       << ",\"kk\":" << op->k << ",\"ratio\":" << op->dropout_ratio << ",\"eltwise\":" << jstr(op->eltwise_op) << ",\"relu\":" << (op->fused_relu ? 1 : 0)
       << "}";
   }
+  // the backward ops (--add-bck-ops), after the forward ones: dims are those of each top ("" = none)
+  for (auto const &op : cp.bck_ops) {
+    o << ",{\"type\":" << jstr(op->type) << ",\"tag\":" << jstr(op->tag) << ",\"bck\":1,\"bots\":[";
+    for (size_t i = 0; i < op->bots.size(); ++i) o << (i ? "," : "") << jstr(op->bots[i]);
+    o << "],\"tops\":[";
+    for (size_t i = 0; i < op->tops.size(); ++i) o << (i ? "," : "") << jstr(op->tops[i]);
+    o << "],\"top_dims\":[";
+    for (size_t i = 0; i < op->tops.size(); ++i)
+      o << (i ? "," : "") << (op->tops[i].empty() ? std::string("[]") : jdims(cp.node_dims.at(op->tops[i])));
+    o << "]}";
+  }
   o << "],\"ignored\":[";
   for (size_t i = 0; i < cp.ignored.size(); ++i) o << (i ? "," : "") << jstr(cp.ignored[i]);
   o << "]}";
@@ -98,7 +116,7 @@ int main(int argc, char **argv) {
   uint32_t img = 0, iters = 3, blob_sample = 0;
   int device = 0;
   bool plan = false, plan_js = false, plan_exec = false, pack = true, fold = true, inplace = true, resadd = true;
-  bool det_dropout = false;
+  bool det_dropout = false, add_bck = false;
   uint32_t graph_reps = 0, drop_seed = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -128,7 +146,8 @@ int main(int argc, char **argv) {
     else if (a == "--det-dropout") {
       det_dropout = true;
       drop_seed = (uint32_t)strtoul(val().c_str(), nullptr, 0);
-    } else if (a == "--mode-args") mode_args = val();
+    } else if (a == "--add-bck-ops") add_bck = true;
+    else if (a == "--mode-args") mode_args = val();
     else {
       fprintf(stderr, "unknown argument %s\n", a.c_str());
       return 2;
@@ -137,12 +156,12 @@ int main(int argc, char **argv) {
   if (net.empty()) {
     fprintf(stderr, "usage: boda_hip_rtc_fwd --net <prototxt> [--img N] [--out-node n] [--iters K] "
                     "[--plan|--plan-json|--plan-exec] [--save DIR] [--save-blobs DIR [--blob-sample N]] [--device d] "
-                    "[--no-pack] [--no-fold] [--no-inplace-concat] [--no-resadd] [--graph R] [--det-dropout SEED] "
+                    "[--no-pack] [--no-fold] [--no-inplace-concat] [--no-resadd] [--graph R] [--det-dropout SEED] [--add-bck-ops] "
                     "[--mode-args (k=v,...)]\n");
     return 2;
   }
   try {
-    p_conv_pipe_t cp = create_pipe_from_prototxt(read_file(net), img, out_node, det_dropout);
+    p_conv_pipe_t cp = create_pipe_from_prototxt(read_file(net), img, out_node, det_dropout, add_bck);
     if (plan_exec) {  // the executor's folds / in-place Concat slabs (no GPU)
       conv_pipe_fwd_t fwd;
       fwd.cp = cp;
@@ -160,7 +179,9 @@ int main(int argc, char **argv) {
       }
       return 0;
     }
-    if (cp->inputs.size() != 1) rt_err("nets with one data input are supported");
+    if (cp->inputs.size() != (cp->label_node.empty() ? 1u : 2u) || cp->inputs[0] == cp->label_node)
+      rt_err("nets with one data input are supported");
+    if (add_bck && cp->label_node.empty()) rt_err("--add-bck-ops: the net has no Data layer with a label top");
     // the mode's init arguments (NESI's name -> lexp map)
     nesi_init_arg_t nia(mode_args.empty() ? nullptr : parse_lexp(mode_args));
     nia.set("rtc", "(be=hip,device=" + std::to_string(device) + ")");
@@ -171,7 +192,7 @@ int main(int argc, char **argv) {
     if (graph_reps) nia.set("graph_reps", std::to_string(graph_reps));
     p_has_conv_fwd_t fwd = make_p_has_conv_fwd_t("rtc");
     fwd->init(cp, &nia);
-    if (det_dropout) fwd->set_det_drop_seed(drop_seed);
+    if (det_dropout || add_bck) fwd->set_det_drop_seed(drop_seed);
 
     std::string const in_vn = cp->inputs[0];
     auto in = std::make_shared<nda_t>(cp->node_dims.at(in_vn));
@@ -184,13 +205,30 @@ int main(int argc, char **argv) {
       for (auto const &op : cp->ops)
         for (auto const &t : op->tops)
           if (seen.insert(t).second) gets.push_back(t);
+      for (auto const &op : cp->bck_ops)
+        for (auto const &t : op->tops)
+          if (!t.empty() && seen.insert(t).second) gets.push_back(t);
     }
     p_map_str_p_nda_t fmap = std::make_shared<map_str_p_nda_t>();
     (*fmap)[in_vn] = in;
+    vect_string sets{in_vn};
+    if (add_bck) {  // the synthetic labels
+      uint32_t C = 1;
+      for (auto const &op : cp->ops)
+        if (op->type == "SoftmaxWithLoss") {
+          C = cp->node_dims.at(op->bots[0]).dsz("chan");
+          break;
+        }
+      auto lab = std::make_shared<nda_t>(cp->node_dims.at(cp->label_node));
+      for (uint64_t i = 0; i < lab->dims.elems(); ++i)
+        lab->elems()[i] = std::min((float)(C - 1), std::floor((det_hash_rand((uint32_t)i + 90417263u) + 5.0f) / 10.0f * C));
+      (*fmap)[cp->label_node] = lab;
+      sets.push_back(cp->label_node);
+    }
     std::string best_log;
     double best = 1e30;
     for (uint32_t it = 0; it < std::max(1u, iters); ++it) {
-      fwd->run_fwd({in_vn}, fmap, gets);
+      fwd->run_fwd(sets, fmap, gets);
       std::string log = fwd->get_info_log();
       // "forward <ms> ms" line of the info log: keep the fastest forward's log
       size_t p = log.find("\nforward ");

@@ -129,6 +129,8 @@ int bh_capture_trace(bh_ctx *ctx, uint32_t *out, uint32_t cap, uint32_t *n);
 #define BH_GEN_CONV_FILTS 3
 #define BH_GEN_CONV_BIASES 4
 #define BH_GEN_BCK_OUT_GRAD 5 /* out_grad_loss img:chan:y:x d = {B, OC, OH, OW}: BH_GEN_CONV_IN's modes, a seed of its own */
+#define BH_GEN_COND 6  /* ZeroIfNonPos cond img:chan:y:x: BH_GEN_CONV_IN's modes, a seed of its own */
+#define BH_GEN_LABEL 7 /* SoftmaxWithLoss label img:y:x, d = {B, H, W, C}: hashed integers in [0, C), any mode */
 int bh_gen_data(bh_ctx *ctx, int kind, float *dst, const uint32_t dims[4], uint32_t mode, float vi);
 
 /* ---- the hot path ------------------------------------------------------
@@ -287,6 +289,60 @@ int bh_softmax_chans(bh_ctx *ctx, const float *in, float *prob, uint32_t B, uint
  * (test/rtc/split_copy.cucl, icix). */
 int bh_chan_copy(bh_ctx *ctx, const float *in, float *out, uint32_t B, uint32_t HW, uint32_t in_c, uint32_t ic0,
                  uint32_t out_c, uint32_t oc0, uint32_t nc);
+
+/* ---- the backward pass of those layers (add_bck_ops: coi src/conv_util.cc:40-64, emitted at
+ *      src/rtc_fwd.cc:345-404), NCHW fp32 (bh_bckops.hip). BckDropout is bh_dropout_inplace with the
+ *      forward's seed and ratio; Split is bh_chan_copy. The last argument of every entry is its form:
+ *      0 = the production kernel; 1 = "ref64": one thread per output element, double accumulation
+ *      over the true terms, rounded once (the known-good tune of ops-prof sweeps; never routed);
+ *      anything else: BH_UNSUP. Zero-sized dims: BH_UNSUP; a NULL required tensor: BH_ERR. No atomics:
+ *      two calls on the same inputs give the same bits. Inside a capture these are barriers, as
+ *      bh_pool_fwd_nchw / bh_lrn_fwd_nchw are. ---- */
+/* Spreading (test/rtc/spreading.cucl): the backward of bh_pool_fwd_nchw with the same eleven dims;
+ * out_grad and out_in_yx are B x C x OH x OW (bh_pool_out_size), in_grad B x C x H x W. Every element
+ * of in_grad is written; a pixel under no window gets 0.
+ * max (avg=0): in_grad[n][c][y][x] = sum of out_grad over the windows covering (y, x) whose out_in_yx
+ *   equals y*W+x. An entry of -1 propagates nothing; ties go where the forward pointed. (out_in_yx
+ *   is a float: H*W above 2^24 is BH_UNSUP.)
+ * avg (avg=1): the exact adjoint of bh_pool_fwd_nchw: each covering window contributes out_grad /
+ *   (that window's in-image tap count). (The reference divides by KY*KX -- its "FIXME: not right" --
+ *   which is the same wherever windows are whole.) out_in_yx may be NULL.
+ * Summation order: covering windows oy-major, ox-minor. Global pooling: KY=H, KX=W, strides 1. */
+int bh_spreading_nchw(bh_ctx *ctx, const float *out_grad, const float *out_in_yx, float *in_grad, uint32_t B,
+                      uint32_t C, uint32_t H, uint32_t W, uint32_t KY, uint32_t KX, uint32_t sy, uint32_t sx,
+                      uint32_t py, uint32_t px, int avg, int form);
+/* BckLRN (test/rtc/bck_lrn.cucl). Per pixel, with t[c] = out_grad[c]*out[c]/out_scale_base[c]:
+ *   in_grad[c] = out_grad[c]*out_scale_base[c]^-beta
+ *                + in[c] * (-2*beta*alpha/local_size) * sum of t[c'] over |c'-c| <= local_size/2, 0 <= c' < C
+ * in, out, out_scale_base: the forward's (bh_lrn_fwd_nchw; out_scale_base is required; k is inside
+ * it). local_size odd and <= 11, else BH_UNSUP. Each window sums in ascending channel order. */
+int bh_lrn_bck_nchw(bh_ctx *ctx, const float *in, const float *out, const float *out_scale_base,
+                    const float *out_grad, float *in_grad, uint32_t B, uint32_t C, uint32_t H, uint32_t W,
+                    uint32_t local_size, float alpha, float beta, float k, int form);
+/* ZeroIfNonPos (test/rtc/ZeroIfNonPos.cucl; ReLU's backward with cond = the ReLU's output):
+ * out = cond > 0 ? in : 0 as a select: a NaN cond gives 0, and a NaN in under cond <= 0 gives 0.
+ * out may alias in. n elements. */
+int bh_zero_if_non_pos(bh_ctx *ctx, const float *in, const float *cond, float *out, uint64_t n, int form);
+/* Reduce (test/rtc/reduce.cucl): out = ((0 + ins[0]) + ins[1]) + ..., in that order, over n elements;
+ * ins is a host array of n_ins device pointers, 1 <= n_ins <= 8, else BH_UNSUP. */
+int bh_reduce_sum(bh_ctx *ctx, const float *const *ins, uint32_t n_ins, float *out, uint64_t n, int form);
+/* sm_grad_and_loss (test/rtc/sm_grad_and_loss.cucl). prob, in_grad: B x C x H x W; label,
+ * loss_per_pel: B x H x W. With l = (int)label[n][y][x] (per-pixel labels; the reference indexes
+ * label[n], the same thing at the 1x1 maps it runs on):
+ *   loss_per_pel[n][y][x] = -log(max(prob[n][l][y][x], FLT_MIN)),  in_grad = (prob - [c==l]) / B.
+ * A label outside [0, C), or NaN, reads nothing outside the tensor: that pixel's loss_per_pel and
+ * its gradient column become NaN, so the error shows. */
+int bh_sm_grad_and_loss(bh_ctx *ctx, const float *prob, const float *label, float *in_grad, float *loss_per_pel,
+                        uint32_t B, uint32_t C, uint32_t H, uint32_t W, int form);
+/* sum_loss_over_imgs (test/rtc/sum_loss_over_imgs.cucl): loss[y][x] = (sum of loss_per_pel[n][y][x],
+ * n ascending) / B; HW = H*W pixels. */
+int bh_sum_loss_over_imgs(bh_ctx *ctx, const float *loss_per_pel, float *loss, uint32_t B, uint32_t HW, int form);
+/* SoftmaxWithLoss as ONE call for bh_time_next_call (three dispatches): bh_softmax_chans(in, prob),
+ * bh_sm_grad_and_loss, bh_sum_loss_over_imgs; bit-identical to those three called in turn (softmax
+ * has one form; the other two take form). */
+int bh_softmax_with_loss(bh_ctx *ctx, const float *in, const float *label, float *prob, float *in_grad,
+                         float *loss_per_pel, float *loss, uint32_t B, uint32_t C, uint32_t H, uint32_t W,
+                         int form);
 
 /* Beyond the reference's rtc_fwd (it rejects these), for resnet nets:
  * per-channel affine out = in * scale[c] + shift[c] (+ReLU) -- inference BatchNorm
